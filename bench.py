@@ -7,12 +7,18 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W           # what the driver does
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does set-up, warm-up, the timed steps and
+nothing else: `metric`, `value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step` (milliseconds of one timed step).
+    --dump-outputs DIR   after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy
+                         (float32 / float64, at most 64 MB in all: a fixed seeded sample of anything larger)
+    --full               also the measurements below (parity of the timed configuration, eager launch, the other
+                         precision, B=1 latency, CPU / PyTorch-ROCm eager baselines, the other BASELINE workloads)
+With --full the line also holds
   roofline     : the dominant kernel (3x3x3 conv 32->32 @ 48x136x240), timed live with HIP events on the launch
                  stream in an instrumented replay of the same forward; `rooflines` holds the same record for the
                  volume builder (HBM), the 2-D backbone (MFMA), the fused soft-argmin head (HBM) and the classifier
-  cpu_baseline : the CPU path on this box's host cores (rank 0, N=1): the REAL reference modules through the import
-                 shim when /root/reference is mounted ("reference"), else the oracle restatement ("port");
+  cpu_baseline : the CPU path on the host cores (rank 0, N=1): the REAL reference modules through the import shim when
+                 $OPENSTEREO_REF names a reference checkout ("reference"), else the oracle restatement ("port");
                  1 warm-up + 3 timed full-size pairs, median, per-stage split
 Other workloads (BASELINE configs [2]-[4]; same JSON contract, their own metric string):
   --workload lightstereo_kitti15   correlation volume -> 2-D aggregation -> soft-argmin -> convex upsample, 384x1248
@@ -97,13 +103,18 @@ def parse():
                              "stereobase_e2e", "igev_e2e", "lightstereo_e2e"))
     ap.add_argument("--precision", choices=("f16x3", "f32", "f16"), default=os.environ.get("OSA_PRECISION", "f16x3"),
                     help="MFMA arithmetic mode of the conv kernels (both pass the same parity tests)")
-    ap.add_argument("--stages", default="", help="write the full per-stage timing table to this file")
+    ap.add_argument("--stages", default="", help="with --full: write the full per-stage timing table to this file")
     ap.add_argument("--amp", action="store_true", help="run the step the way the reference runs its AMP configs: inference inside torch.autocast(fp16); training as autocast + GradScaler (trainer_template.py:211-226) -- engine layers in the native f16 mode")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from Python instead of replaying a hipGraph")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU leg (default workload) / the same-GPU PyTorch-ROCm eager leg (training workloads)")
     ap.add_argument("--no-workloads", action="store_true", help="default workload: skip the compact measurements of the other BASELINE configs (`workloads`)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline figure: timed-configuration parity, eager and "
+                         "other-precision legs, B=1 latency, rooflines, CPU / PyTorch-ROCm eager baselines, the other BASELINE workloads")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--timed-only", action="store_true",
-                    help="profiling runs: nothing but warm-up + the timed configuration (no other-precision leg, no B=1 loop, no CPU leg)")
+                    help="profiling runs: nothing but warm-up + the timed configuration, even with --full (the default without --full)")
     ap.add_argument("--force-ddp", action="store_true", help="training workloads on ONE GPU: one-rank RCCL process group + DistributedDataParallel (checks the DDP + hipGraph path without a second GPU)")
     ap.add_argument("--stub", action="store_true",
                     help="CPU plumbing self-test (tests/test_sharding_gloo.py): gloo backend, the forward replaced by a sleep")
@@ -114,6 +125,7 @@ def parse():
 class GwcNetInference:
     metric = "stereo-pairs/s at 540x960 D=192 (GwcNet fwd)"
     scaling, graphable, training = "weak", True, False
+    output_name = "disp_pred"
 
     def __init__(self, args, dev, rank):
         from openstereo_amd.models.gwcnet import GwcNet
@@ -291,6 +303,7 @@ class _E2EInference:
     (feature_pyramid.py: MobileNetV2-100 trunk mirror -- unpinned, timm absent -- + the reference-written FPN decoder, pinned), all of it
     on the engine in eval mode."""
     scaling, graphable, training = "weak", True, False
+    output_name = "disp_pred"
     H, W = 544, 960
 
     def _finish(self, net, args, dev, rank, seed, scale255=False):
@@ -729,6 +742,37 @@ def _time_steps(step, steps, warmup):
     return (time.perf_counter() - t0) / steps, out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def step_outputs(wl, out):
+    """What a caller of the timed step receives, by name: the disparity of an inference workload; the loss of a training workload and the
+    parameters its optimizer step has just written (flattened in parameters() order)."""
+    if getattr(wl, "training", False):
+        return {"loss": out, "parameters": torch.cat([p.detach().float().flatten() for p in wl.raw.parameters()])}
+    return {getattr(wl, "output_name", "disp"): out}
+
+
+def dump_outputs(outputs, folder, budget=DUMP_BUDGET_BYTES):
+    """Write every tensor as folder/<name>.npy (float64 stays float64, everything else float32).  An array that does not fit into what is left
+    of the byte budget is written as a fixed seeded sample of its flattened elements (same positions in every run of the same arguments)."""
+    import numpy as np
+    os.makedirs(folder, exist_ok=True)
+    left, written = budget, {}
+    for name, t in outputs.items():
+        a = t.detach().cpu()
+        a = a.double() if a.dtype == torch.float64 else a.float()
+        a = a.numpy()
+        cap = left // a.itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=int(cap), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(folder, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
+
+
 def eager_training_baseline(name, args, dev, rank, steps=3, warmup=2):
     """`pytorch_rocm_eager_same_gpu` for a training workload: the same class, optimizer, crop and batch, with every hot-path op executed by
     stock PyTorch-ROCm (see _eager_torch_mode).  MIOpen's find mode runs during the warm-up steps."""
@@ -822,9 +866,9 @@ def gwcnet_cpu_baseline(wl, gpu_out):
     restatement; fp32, no_grad, all host cores, 1 warm-up + 3 timed full-size pairs, median, per-stage split."""
     from oracle import torch_ref as O           # CPU-baseline leg only (the checker / the "port")
     Lc, Rc, sd = wl.L[:1].cpu(), wl.R[:1].cpu(), wl.sd
-    ref_root = os.environ.get("OPENSTEREO_REF", "/root/reference")
+    ref_root = os.environ.get("OPENSTEREO_REF")
     kind, run = "port", None
-    if os.path.isdir(os.path.join(ref_root, "stereo")):
+    if ref_root and os.path.isdir(os.path.join(ref_root, "stereo")):
         try:
             import importlib
             from openstereo_amd import attach
@@ -1001,6 +1045,10 @@ def main():
     dt = reduce_step_time(time.perf_counter() - t0, dev)       # MAX over ranks
     assert torch.isfinite(out).all()
     rate = whole_job_rate(B, args.steps, world, dt)
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(step_outputs(wl, out), args.dump_outputs)
+        print(f"[bench] outputs of the last timed step written to {args.dump_outputs}: {shapes}", file=sys.stderr)
+    extras = args.full and not args.timed_only        # everything beyond the headline figure
 
     line = {"metric": wl.metric, "value": round(rate, 3), "unit": "stereo-pairs/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": wl.scaling,
@@ -1016,14 +1064,14 @@ def main():
     if args.workload == "gwcnet" and not args.stub and rank == 0:
         from openstereo_amd import engine
         roofs, alt, latency_1, cpu = [], None, None, None
-        if not args.timed_only and world == 1:
+        if extras and world == 1:
             cfg["timed_config_parity"] = gwcnet_timed_config_parity(wl, step)      # every pair of the timed step vs single-pair single-stream runs
             # the same maxima as scalar keys: the driver's parsed copy of `config` keeps scalars only
             tp = cfg["timed_config_parity"]
             cfg.update({"parity_replay_vs_replay_max_px": tp["replay_vs_replay_max_px"], "parity_vs_one_stream_max_px": tp["vs_same_sub_batches_on_one_stream_max_px"],
                         "parity_vs_single_pair_runs_max_px": tp["vs_single_pair_runs_max_px"], "parity_worst_pair_epe_px": tp["vs_single_pair_runs_worst_pair_epe_px"],
                         "parity_all_finite": tp["all_finite"]})
-        if not args.timed_only:
+        if extras:
             nrep = max(2, min(args.steps, 5))
             if graph is not None and world == 1:
                 # like for like with the reference's loops, which launch eagerly: the same step, same arithmetic mode, no graph
@@ -1088,18 +1136,18 @@ def main():
         line["rooflines"] = roofs[1:]
         line["cpu_baseline"] = cpu
         line["other_precision"] = alt
-        if not args.timed_only and world == 1 and not args.no_workloads:
+        if extras and world == 1 and not args.no_workloads:
             del wl
             torch.cuda.empty_cache()
             line["workloads"] = secondary_workloads(args, dev, rank)
     elif rank == 0:
         line["roofline"], line["cpu_baseline"] = None, None
-        if not args.stub and not args.timed_only and dev.type == "cuda":
+        if not args.stub and extras and dev.type == "cuda":
             roofs, per_step = generic_rooflines(wl, args, eager_step, max(2, min(args.steps, 3)))
             cfg["stage_ms_per_step"] = dict(list(per_step.items())[:14])
             line["roofline"] = roofs[0] if roofs else None
             line["rooflines"] = roofs[1:]
-            line["cpu_baseline_note"] = "the CPU leg runs with the default workload only (bench.py without --workload)"
+            line["cpu_baseline_note"] = "the CPU leg runs with the default workload only (bench.py --full without --workload)"
             if wl.training and world == 1 and not args.no_cpu_baseline:
                 del wl
                 torch.cuda.empty_cache()

@@ -592,13 +592,34 @@ def gen_e2e_dormant():
     save("e2e_dormant.npz", **out)
 
 
+def gen_reference_keys():
+    """Parameter names + shapes of the reference's models (tests/test_attach_wiring_cpu.py's checkpoint-key cases) and of its
+    MultiBasicEncoder (tests/test_context_encoder.py): reference_keys.json."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_attach_wiring_cpu as W
+    keys = W.live_reference_keys()
+    sys.modules.setdefault("timm", types.ModuleType("timm"))
+    from stereo.modeling.models.igev.extractor import MultiBasicEncoder
+    enc = MultiBasicEncoder(output_dim=[[128, 128, 128]] * 2, norm_fn="batch", downsample=2)
+    keys["context_encoder"] = {k: tuple(v.shape) for k, v in enc.state_dict().items()}
+    path = os.path.join(HERE, "reference_keys.json")
+    with open(path, "w") as f:
+        json.dump({n: {k: list(v) for k, v in d.items()} for n, d in sorted(keys.items())}, f, indent=0)
+        f.write("\n")
+    print(f"wrote reference_keys.json: {os.path.getsize(path) / 1e6:.2f} MB")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--full", action="store_true")
-    ap.add_argument("--only", default="", help="regenerate a single fixture group: lightstereo | igev_update | at_size | preprocess | dormant | e2e | e2e_dormant | e2e_train_at_size | feature_pyramid | unit_gain | context_encoder")
+    ap.add_argument("--only", default="", help="regenerate a single fixture group: lightstereo | igev_update | at_size | preprocess | dormant | e2e | e2e_dormant | e2e_train_at_size | feature_pyramid | unit_gain | context_encoder | reference_keys")
     args = ap.parse_args()
     import_reference()
     torch.set_grad_enabled(False)
+    if args.only == "reference_keys":
+        gen_reference_keys()
+        return
     from openstereo_amd.utils.weights import synth_state_dict, synth_images
     if args.only == "lightstereo":
         gen_lightstereo()

@@ -33,7 +33,7 @@ if os.path.exists(s):
     keep = [l for l in open(s, errors="replace") if not l.startswith(("GridwiseOp", "MIOpen(HIP)"))]
     open(os.path.join(P, "final_gpu_suite.txt"), "w").writelines(keep[-40:])
     print("copied final_gpu_suite.txt:", keep[-1].strip())
-# the default bench line: exactly one JSON object (stdout of `python bench.py --gpus 1 --steps 20 --warmup 5`)
+# the default bench line: exactly one JSON object (stdout of `python bench.py --gpus 1 --steps 20 --warmup 5 --full`)
 b = os.path.join(G, "r5_final", "bench_default.json")
 if os.path.exists(b):
     lines = [l for l in open(b, errors="replace").read().splitlines() if l.strip()]
