@@ -3,9 +3,10 @@ arguments, the current HIP stream and TORCH_CHECK errors (north_star: "exposed t
 SURVEY 8b).  Built in-tree next to the C-ABI library (`python -m openstereo_amd.build`: one g++ invocation against torch's headers, ~12 s)
 as openstereo_amd/lib/libosa_torch_ext.so, which links libopenstereo_amd.so through $ORIGIN.
 
-`ops` is the loaded namespace or None.  The Python layer (ops.py, engine.PackedConv3d) routes its hot launches through it when present;
-without it the same entry points are reached through ctypes (`_lib.py`) -- the extension adds no kernels and no fallbacks, it replaces
-argument marshalling.  OSA_TORCH_EXT=0 keeps it unloaded (A/B of the two dispatch paths)."""
+Every kernel launch of the package goes through this namespace: the extension is required, like the C-ABI library itself, and `load()`
+raises when it is missing or stale.  It adds no kernels of its own.  It is loaded from the directory of the C-ABI library in use
+(`_lib.LIB_PATH`), so an A/B variant (OSA_LIB_PATH=<dir>/libopenstereo_amd.so, tools/build_variant.sh) is a directory holding the
+variant library and a copy of libosa_torch_ext.so, which binds to the library beside it."""
 from __future__ import annotations
 
 import os
@@ -15,7 +16,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 EXT_PATH = os.path.join(_HERE, "lib", "libosa_torch_ext.so")
 SRC = os.path.join(_HERE, "csrc", "torch_ext.cpp")
-ops = None
+ops = None      # the loaded `torch.ops.osa_native` namespace
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
@@ -42,18 +43,21 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
 
 def load():
-    """torch.ops.load_library (once).  Returns the `torch.ops.osa_native` namespace, or None when the extension is not built / switched off."""
+    """torch.ops.load_library (once) of the extension beside the C-ABI library in use.  Returns the `torch.ops.osa_native` namespace; raises
+    _lib.EngineError when the extension is not built or was built against another ABI."""
     global ops
     if ops is not None:
         return ops
-    if os.environ.get("OSA_TORCH_EXT", "1") == "0" or os.environ.get("OSA_LIB_PATH") or not os.path.exists(EXT_PATH):
-        return None          # (OSA_LIB_PATH: an A/B build of the C-ABI library is in use -- the extension links the shipped one)
     import torch
     from . import _lib
     _lib.load()              # the C-ABI library first: a missing / stale one is reported by its own loader
-    torch.ops.load_library(EXT_PATH)
+    path = os.path.join(os.path.dirname(_lib.LIB_PATH), "libosa_torch_ext.so")
+    if not os.path.exists(path):
+        raise _lib.EngineError(f"{path} is missing: build it with `python -m openstereo_amd.build` (g++ against torch's headers). "
+                               "Every launch goes through it.")
+    torch.ops.load_library(path)
     ns = torch.ops.osa_native
     if int(ns.abi_version()) != _lib.abi_version():
-        raise _lib.EngineError(f"libosa_torch_ext.so was built against ABI {int(ns.abi_version())}: rebuild with `python -m openstereo_amd.build`")
+        raise _lib.EngineError(f"{path} was built against ABI {int(ns.abi_version())}: rebuild with `python -m openstereo_amd.build`")
     ops = ns
     return ops

@@ -1,7 +1,7 @@
-"""ctypes binding of the C-ABI library (include/openstereo_amd.h).
+"""ctypes binding of the C-ABI library (include/openstereo_amd.h): the loader, the ABI check and the host-side size queries.
 
-The product path has NO fallback: if the gfx950 library is missing or a call fails, a
-RuntimeError is raised.  Nothing in here imports the CPU oracle.
+The package launches every kernel through the C++ extension (_ext.py); `call` serves the C-ABI tests and C-ABI users.  There is
+NO fallback: if the gfx950 library is missing or a call fails, a RuntimeError is raised.  Nothing in here imports the CPU oracle.
 """
 from __future__ import annotations
 
@@ -10,7 +10,8 @@ import os
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("OSA_LIB_PATH") or os.path.join(_HERE, "lib", "libopenstereo_amd.so")   # override: A/B experiments only
+# override: A/B experiments only -- a variant directory holding its libopenstereo_amd.so and a copy of libosa_torch_ext.so (_ext.py)
+LIB_PATH = os.environ.get("OSA_LIB_PATH") or os.path.join(_HERE, "lib", "libopenstereo_amd.so")
 
 _lock = threading.Lock()
 _lib = None
@@ -230,19 +231,14 @@ def load():
                 "(hipcc, gfx950). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)   # AttributeError if the .so does not export it
-            except AttributeError:
-                if os.environ.get("OSA_LIB_PATH"):      # A/B experiment builds may predate an entry point; the shipped library may not
-                    continue
-                raise
+            fn = getattr(lib, name)       # AttributeError if the .so does not export it
             fn.restype = res
             fn.argtypes = args
         if lib.osa_abi_version() != abi_version(lib):
             raise EngineError(f"ABI version mismatch: library reports {lib.osa_abi_version()}, include/openstereo_amd.h declares {abi_version(lib)}")
-        if os.environ.get("OSA_B_RING_MASK") and hasattr(lib, "osa_conv_b_ring_mask"):
+        if os.environ.get("OSA_B_RING_MASK"):
             lib.osa_conv_b_ring_mask(int(os.environ["OSA_B_RING_MASK"], 0))     # A/B runs: which tiles take their weights through the LDS ring
-        if os.environ.get("OSA_VOL_WALK") and hasattr(lib, "osa_volume_walk_step"):
+        if os.environ.get("OSA_VOL_WALK"):
             lib.osa_volume_walk_step(int(os.environ["OSA_VOL_WALK"]))               # A/B runs: 0 = chunked volume builder, 4 / 8 = d-walking form
         _lib = lib
     return _lib
@@ -270,7 +266,7 @@ def abi_version(lib=None) -> int:
     return _abi
 
 
-CALLS = {}          # name -> number of calls that went through ctypes (the C++ extension's dispatcher calls do not pass here): tests / DESIGN.md count them
+CALLS = {}          # name -> number of calls that went through ctypes (the C++ extension's dispatcher calls do not pass here): the package makes none
 
 
 def call(name: str, *args):

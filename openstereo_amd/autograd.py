@@ -14,15 +14,14 @@ unchanged (one process per GPU).
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 import threading
 
 import torch
 
-from . import _lib, amp, engine, ops, timing
-from .ops import _f32c, _p, _stream, channel_sums, cl_rows, empty_cl, is_cl, to_cl
+from . import _ext, _lib, amp, engine, ops, timing
+from .ops import _f32c, channel_sums, cl_rows, empty_cl, is_cl, to_cl
 from .ranges import input_meta, attach_meta
 
 
@@ -49,14 +48,7 @@ class _GwcVolume(torch.autograd.Function):
         l, r = ctx.saved_tensors
         maxdisp, G, dt = ctx.meta
         B, C, H, W = l.shape
-        dv = _f32c(dvol)
-        ext = engine._ext.load()
-        if ext is not None:
-            dl, dr = ext.volume_bwd(dv, l, r, [B, C, H, W], maxdisp, G, False, True)
-            return dl.to(dt), dr.to(dt), None, None
-        dl, dr = torch.empty_like(l), torch.empty_like(r)
-        _lib.call("osa_build_volume_bwd_f32", dv.data_ptr(), l.data_ptr(), r.data_ptr(), dl.data_ptr(), dr.data_ptr(),
-                  B, C, H, W, maxdisp, G, 0, 1, G, 0, _stream())
+        dl, dr = _ext.load().volume_bwd(_f32c(dvol), l, r, [B, C, H, W], maxdisp, G, False, True)
         return dl.to(dt), dr.to(dt), None, None
 
 
@@ -72,15 +64,7 @@ class _ConcatVolume(torch.autograd.Function):
     @_bwd
     def backward(ctx, dvol):
         maxdisp, mask_left, dt, (B, C, H, W) = ctx.meta
-        dv = _f32c(dvol)
-        ext = engine._ext.load()
-        if ext is not None:
-            dl, dr = ext.volume_bwd(dv, None, None, [B, C, H, W], maxdisp, 0, True, bool(mask_left))
-            return dl.to(dt), dr.to(dt), None, None
-        dl = torch.empty((B, C, H, W), device=dv.device, dtype=torch.float32)
-        dr = torch.empty_like(dl)
-        _lib.call("osa_build_volume_bwd_f32", dv.data_ptr(), None, None, dl.data_ptr(), dr.data_ptr(),
-                  B, C, H, W, maxdisp, 0, 1, 1 if mask_left else 0, 2 * C, 0, _stream())
+        dl, dr = _ext.load().volume_bwd(_f32c(dvol), None, None, [B, C, H, W], maxdisp, 0, True, bool(mask_left))
         return dl.to(dt), dr.to(dt), None, None
 
 
@@ -108,14 +92,7 @@ class _SoftArgmin(torch.autograd.Function):
     @staticmethod
     @_bwd
     def backward(ctx, dout):
-        B, D, H, W = ctx.shape
-        g = _f32c(dout)
-        ext = engine._ext.load()
-        if ext is not None:
-            return ext.softargmin_bwd(g, D)
-        dp = torch.empty(ctx.shape, device=g.device, dtype=torch.float32)
-        _lib.call("osa_softargmin_bwd_f32", g.data_ptr(), dp.data_ptr(), B, D, H, W, _stream())
-        return dp
+        return _ext.load().softargmin_bwd(_f32c(dout), ctx.shape[1])
 
 
 class _SoftmaxSoftArgmin(torch.autograd.Function):
@@ -130,14 +107,7 @@ class _SoftmaxSoftArgmin(torch.autograd.Function):
     @_bwd
     def backward(ctx, dout):
         (c,) = ctx.saved_tensors
-        B, D, H, W = c.shape
-        g = _f32c(dout)
-        ext = engine._ext.load()
-        if ext is not None:
-            return ext.softmax_softargmin_bwd(c, g)
-        dc = torch.empty_like(c)
-        _lib.call("osa_softmax_softargmin_bwd_f32", c.data_ptr(), g.data_ptr(), dc.data_ptr(), B, D, H, W, _stream())
-        return dc
+        return _ext.load().softmax_softargmin_bwd(c, _f32c(dout))
 
 
 class _UpsampleSoftArgmin(torch.autograd.Function):
@@ -154,17 +124,7 @@ class _UpsampleSoftArgmin(torch.autograd.Function):
     def backward(ctx, dout):
         (c,) = ctx.saved_tensors
         maxdisp, h, w, align = ctx.meta
-        B, Dl, Hl, Wl = c.shape
-        g = _f32c(dout)
-        ext = engine._ext.load()
-        if ext is not None:
-            return ext.upsample_softargmin_bwd(c, g, int(maxdisp), int(h), int(w), bool(align)), None, None, None, None
-        dc = torch.empty_like(c)
-        need = _lib.load().osa_upsample_softargmin_bwd_workspace_bytes(B, Dl, int(h), int(w))     # [B,Dl,H,W] scratch: atomic-free, deterministic
-        ws = torch.empty((need + 3) // 4, device=c.device, dtype=torch.float32)
-        _lib.call("osa_upsample_softargmin_bwd_ws_f32", c.data_ptr(), g.data_ptr(), dc.data_ptr(), B, Dl, Hl, Wl,
-                  int(maxdisp), int(h), int(w), 1 if align else 0, ws.data_ptr(), need, _stream())
-        return dc, None, None, None, None
+        return _ext.load().upsample_softargmin_bwd(c, _f32c(dout), int(maxdisp), int(h), int(w), bool(align)), None, None, None, None
 
 
 def disparity_regression(prob, maxdisp, keepdim=True):
@@ -260,90 +220,39 @@ def _pack_now(w, Ci, Co, k, mode, precision):
     Returns (packed buffer, scale): f32 -> scale 1.0; f16x3 -> a 2-float DEVICE tensor {wscale, 1 / wscale} that the pack kernel derived
     from max |w| on the device (osa_*_pack_*_auto) -- no host synchronisation per layer / role / optimizer step, and the whole training
     step can be captured in a hipGraph (the packs are part of the captured work)."""
-    f16 = precision == "f16x3"
-    h16 = precision == "f16"            # native fp16 operands (AMP training, r5): weights rounded to nearest even, no scale
+    f16 = precision == "f16x3"          # (precision "f16": native fp16 operands, AMP training, r5: weights rounded to nearest even, no scale)
     lib = _lib.load()
-    ext = engine._ext.load()
-    if ext is not None:
-        # PyTorch-ROCm C++ extension (csrc/torch_ext.cpp conv_pack / deconv_pack): the same pack kernels, one dispatcher call
-        amax = sc = None
-        if f16:
-            amax = torch.linalg.vector_norm(w.detach(), float("inf")).reshape(1)
-            sc = torch.empty(2, device=w.device, dtype=torch.float32)
-        pid = _PREC_ID[precision]
-        if mode in ("deconv2d", "deconv"):
-            n = (lib.osa_deconv2d_packed_floats if mode == "deconv2d" else lib.osa_deconv3d_packed_floats)(Ci, Co, k[0])
-            buf = torch.zeros(n, device=w.device, dtype=torch.float32)
-            ext.deconv_pack(w, buf, [Ci, Co, k[0], 1, 1 if mode == "deconv2d" else 0], pid, amax, sc)
-        else:
-            n = lib.osa_conv3d_packed_floats(Ci, Co, *k)
-            buf = torch.zeros(n, device=w.device, dtype=torch.float32)
-            tr, fl = {"fwd": (0, 0), "dgrad_s1": (1, 1), "dgrad_of_deconv": (0, 0)}[mode]
-            ext.conv_pack(w, buf, [Ci, Co, k[0], k[1], k[2], tr, fl], pid, amax, sc)
-        return buf, (sc if f16 else 1.0)
+    amax = sc = None
     if f16:
-        amax = torch.linalg.vector_norm(w.detach(), float("inf"))          # one reduction kernel, stays on the device
+        amax = torch.linalg.vector_norm(w.detach(), float("inf")).reshape(1)      # one reduction kernel, stays on the device
         sc = torch.empty(2, device=w.device, dtype=torch.float32)
-    if mode == "deconv2d":
-        n = lib.osa_deconv2d_packed_floats(Ci, Co, k[0])
+    pid = _PREC_ID[precision]
+    # csrc/torch_ext.cpp conv_pack / deconv_pack: one dispatcher call
+    if mode in ("deconv2d", "deconv"):
+        n = (lib.osa_deconv2d_packed_floats if mode == "deconv2d" else lib.osa_deconv3d_packed_floats)(Ci, Co, k[0])
         buf = torch.zeros(n, device=w.device, dtype=torch.float32)
-        if f16:
-            _lib.call("osa_deconv2d_pack_f16x3_auto", w.data_ptr(), buf.data_ptr(), Ci, Co, k[0], 1, amax.data_ptr(), sc.data_ptr(), _stream())
-        elif h16:
-            _lib.call("osa_deconv2d_pack_f16", w.data_ptr(), buf.data_ptr(), Ci, Co, k[0], 1, _stream())
-        else:
-            _lib.call("osa_deconv2d_pack_f32", w.data_ptr(), buf.data_ptr(), Ci, Co, k[0], 1, _stream())
-    elif mode == "deconv":
-        n = lib.osa_deconv3d_packed_floats(Ci, Co, k[0])
-        buf = torch.zeros(n, device=w.device, dtype=torch.float32)
-        if f16:
-            _lib.call("osa_deconv3d_pack_f16x3_auto", w.data_ptr(), buf.data_ptr(), Ci, Co, k[0], 1, amax.data_ptr(), sc.data_ptr(), _stream())
-        elif h16:
-            _lib.call("osa_deconv3d_pack_f16", w.data_ptr(), buf.data_ptr(), Ci, Co, k[0], 1, _stream())
-        else:
-            _lib.call("osa_deconv3d_pack_f32", w.data_ptr(), buf.data_ptr(), Ci, Co, k[0], 1, _stream())
+        _ext.load().deconv_pack(w, buf, [Ci, Co, k[0], 1, 1 if mode == "deconv2d" else 0], pid, amax, sc)
     else:
         n = lib.osa_conv3d_packed_floats(Ci, Co, *k)
         buf = torch.zeros(n, device=w.device, dtype=torch.float32)
         tr, fl = {"fwd": (0, 0), "dgrad_s1": (1, 1), "dgrad_of_deconv": (0, 0)}[mode]
-        if f16:
-            _lib.call("osa_conv3d_pack_ex_auto", w.data_ptr(), buf.data_ptr(), Ci, Co, *k, tr, fl, amax.data_ptr(), sc.data_ptr(), _stream())
-        else:
-            _lib.call("osa_conv3d_pack_ex", w.data_ptr(), buf.data_ptr(), Ci, Co, *k, tr, fl, 2 if h16 else 0, 1.0, _stream())
+        _ext.load().conv_pack(w, buf, [Ci, Co, k[0], k[1], k[2], tr, fl], pid, amax, sc)
     return buf, (sc if f16 else 1.0)
-
-
-def _ranges(x, y, wscale, xmeta=None):
-    """f16x3 operand ranges of a plain conv call: x (activations or incoming gradients -- whose magnitudes are
-    routinely 1e-5 .. 1e-8) is scaled by a power of two derived from its measured max |.| on the device, so the
-    hi/lo fp16 halves keep 22 significant bits whatever the magnitude; exact to undo.  wscale: the packed weights' device-side
-    {scale, 1 / scale} pair (_pack_now)."""
-    return _lib.F16x3Ranges((xmeta if xmeta is not None else input_meta(x)).data_ptr(), None, None, attach_meta(y).data_ptr(), None, None, wscale.data_ptr())
 
 
 _PREC_ID = {"f32": 0, "f16x3": 1, "f16": 2}
 
 
 def _ext_conv(family, x, packed, y, dims, geom, precision, oscale, xmeta=None, scale=None, shift=None):
-    """The plain conv / transposed-conv launch of the training path through the PyTorch-ROCm C++ extension (torch.ops.osa_native.conv_ndhwc:
-    one dispatcher call, tensors in, current HIP stream inside) -- False when the extension is not loaded (the caller then goes through
-    ctypes; same entry point of the C ABI, bit-identical)."""
-    ext = engine._ext.load()
-    if ext is None:
-        return False
+    """The plain conv / transposed-conv launch of the training path (torch.ops.osa_native.conv_ndhwc: one dispatcher call, tensors in, current
+    HIP stream inside).  f16x3: x (activations or incoming gradients -- whose magnitudes are routinely 1e-5 .. 1e-8) is scaled by a power of
+    two derived from its measured max |.| on the device (its range block), so the hi/lo fp16 halves keep 22 significant bits whatever the
+    magnitude; exact to undo.  oscale: the packed weights' device-side {scale, 1 / scale} pair (_pack_now)."""
     metas = []
     if precision == "f16x3":
         e = engine._empty(x.device)
         metas = [xmeta if xmeta is not None else input_meta(x), e, e, attach_meta(y), e, e, oscale]
-    ext.conv_ndhwc(x, 0, packed, scale, shift, None, 0, y, 0, None, dims, geom, family, _PREC_ID[precision], 0, 0.0, 1.0, metas)
-    return True
-
-
-def _sfx_tail(precision, x, y, oscale, xmeta=None):
-    """entry-point suffix and trailing arguments of a plain conv / deconv call in the given arithmetic mode"""
-    if precision == "f16x3":
-        return "f16x3", (1.0, _ranges(x, y, oscale, xmeta), _stream())
-    return ("f16" if precision == "f16" else "f32"), (_stream(),)        # f16: fp32 NDHWC tensors, fp16 operands (no flags, no ranges)
+    _ext.load().conv_ndhwc(x, 0, packed, scale, shift, None, 0, y, 0, None, dims, geom, family, _PREC_ID[precision], 0, 0.0, 1.0, metas)
 
 
 def _alias(t):
@@ -374,12 +283,8 @@ def _run_conv(x, packed, oscale, Ci, Co, k, stride, pad, dil, precision, out_sha
     with timing.span("conv3d", Ci, Co, k[1], stride, D, H, W, flops=2 * macs,
                      nbytes=4 * B * (D * H * W * Ci + out_shape[0] * out_shape[1] * out_shape[2] * Co)):
         scale = None if bias is None else _ones(Co, x.device)
-        if not _ext_conv(0, x, packed, y, [B, D, H, W, Ci4, Cs, Co, CoS, 0, 0],
-                         [k[0], k[1], k[2], stride, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2]], precision, oscale, xmeta, scale, bias):
-            sfx, tail = _sfx_tail(precision, x, y, oscale, xmeta)
-            _lib.call("osa_conv3d_ndhwc_" + sfx, x.data_ptr(), packed.data_ptr(), _p(scale), _p(bias), None, y.data_ptr(),
-                      B, D, H, W, Ci4, Cs, Co, CoS, 0, k[0], k[1], k[2], stride, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2],
-                      None, 0, 0, 0.0, *tail)
+        _ext_conv(0, x, packed, y, [B, D, H, W, Ci4, Cs, Co, CoS, 0, 0],
+                  [k[0], k[1], k[2], stride, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2]], precision, oscale, xmeta, scale, bias)
     return y
 
 
@@ -393,10 +298,7 @@ def _run_deconv(x, packed, oscale, Ci, Co, k, pad, opad, precision):
     Ci4 = (Ci + 3) // 4 * 4
     with timing.span("deconv3d", Ci, Co, k, 2, D, H, W, flops=2 * B * D * H * W * Ci * Co * k ** 3,
                      nbytes=4 * B * (D * H * W * Ci + od(D) * od(H) * od(W) * Co)):
-        if not _ext_conv(1, x, packed, y, [B, D, H, W, Ci4, Cs, Co, CoS, 0, 0], [k, pad, opad], precision, oscale):
-            sfx, tail = _sfx_tail(precision, x, y, oscale)
-            _lib.call("osa_deconv3d_ndhwc_" + sfx, x.data_ptr(), packed.data_ptr(), None, None, None, y.data_ptr(),
-                      B, D, H, W, Ci4, Cs, Co, CoS, 0, k, pad, opad, None, 0, 0, 0.0, *tail)
+        _ext_conv(1, x, packed, y, [B, D, H, W, Ci4, Cs, Co, CoS, 0, 0], [k, pad, opad], precision, oscale)
     return y
 
 
@@ -428,59 +330,30 @@ def _wgrad(xc, dyc, dw, B, D, H, W, Ci, Do, Ho, Wo, Co, k, stride, pad, dil, tra
     xc, dyc = xs[0], dys[0]
     assert precision == "f16" or (xc.dtype == torch.float32 and dyc.dtype == torch.float32), "fp16 tensors exist in the native f16 form only"
     xcs, dycs = (xc.shape[1] if xcs is None else xcs), (dyc.shape[1] if dycs is None else dycs)        # channel strides (rows may be wider than the tensors' logical channels)
-    dims = (B, D, H, W, Ci, Do, Ho, Wo, Co, k[0], k[1], k[2], stride, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2], transposed)
-    lib = _lib.load()
     vox = (D * H * W) if transposed else (Do * Ho * Wo)            # positions every weight tap is accumulated over
     span = dict(flops=2 * B * vox * Ci * Co * k[0] * k[1] * k[2], nbytes=4 * B * (D * H * W * Ci + Do * Ho * Wo * Co))
     if precision == "f16x3" and (xmeta is None or dymeta is None):
         from .ranges import combine_meta
         xmeta = xmeta if xmeta is not None else combine_meta(*[input_meta(t) for t in xs])
         dymeta = dymeta if dymeta is not None else combine_meta(*[input_meta(t) for t in dys])
-    ext = engine._ext.load()
-    if ext is not None:
-        # PyTorch-ROCm C++ extension (csrc/torch_ext.cpp conv_wgrad): workspace query, allocation and launch in one dispatcher call
-        ed = [B, D, H, W, Ci, xcs, Do, Ho, Wo, Co, dycs, k[0], k[1], k[2], stride, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2], transposed]
-        run = (lambda prec, mx, md: ext.conv_wgrad_multi(xs, dys, dw, ed, prec, mx, md)) if multi else (lambda prec, mx, md: ext.conv_wgrad(xs[0], dys[0], dw, ed, prec, mx, md))
-        if precision == "f16" and WGRAD_F16 and ((stride == 1 and not transposed) or WGRAD_F16_CLASS):
-            with timing.span("wgrad_f16", Ci, Co, k[1], stride, D, H, W, transposed, **span):
-                if run(2, None, None):
-                    return
-        if precision == "f16x3" and WGRAD_F16X3 and ((stride == 1 and not transposed) or WGRAD_F16X3_CLASS):
-            with timing.span("wgrad_f16x3", Ci, Co, k[1], stride, D, H, W, transposed, **span):
-                if run(1, xmeta, dymeta):
-                    return
-        if xc.dtype != torch.float32 or dyc.dtype != torch.float32:
-            xs, dys = [t.float() for t in xs], [t.float() for t in dys]      # (dense tensors: .float() keeps the strides the channel strides refer to)
-        with timing.span("wgrad", Ci, Co, k[1], stride, D, H, W, transposed, **span):
-            run(0, None, None)
-        return
-
-    def launch(form, mx, md, need):
-        ws = torch.empty((need + 3) // 4, device=xc.device, dtype=torch.float32)
-        ptrs = lambda ts: (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        _lib.call("osa_conv3d_wgrad_ws_multi", form, ptrs(xs), ptrs(dys), len(xs), dw.data_ptr(), B, D, H, W, Ci, xcs,
-                  Do, Ho, Wo, Co, dycs, k[0], k[1], k[2], stride, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2], transposed,
-                  _p(mx), _p(md), int(xs[0].dtype == torch.float16), int(dys[0].dtype == torch.float16), ws.data_ptr(), need, _stream())
+    # csrc/torch_ext.cpp conv_wgrad: workspace query, allocation and launch in one dispatcher call; False when a split-precision form does
+    # not cover the layer
+    ext = _ext.load()
+    ed = [B, D, H, W, Ci, xcs, Do, Ho, Wo, Co, dycs, k[0], k[1], k[2], stride, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2], transposed]
+    run = (lambda prec, mx, md: ext.conv_wgrad_multi(xs, dys, dw, ed, prec, mx, md)) if multi else (lambda prec, mx, md: ext.conv_wgrad(xs[0], dys[0], dw, ed, prec, mx, md))
     if precision == "f16" and WGRAD_F16 and ((stride == 1 and not transposed) or WGRAD_F16_CLASS):
         # native fp16 operands, one MFMA per product, no range blocks (AMP training: GradScaler owns the range)
-        need = lib.osa_conv3d_wgrad_f16x3_workspace_bytes(*dims)
-        if need:
-            with timing.span("wgrad_f16", Ci, Co, k[1], stride, D, H, W, transposed, **span):
-                launch(2, None, None, need)
-            return
+        with timing.span("wgrad_f16", Ci, Co, k[1], stride, D, H, W, transposed, **span):
+            if run(2, None, None):
+                return
     if precision == "f16x3" and WGRAD_F16X3 and ((stride == 1 and not transposed) or WGRAD_F16X3_CLASS):
-        need = lib.osa_conv3d_wgrad_f16x3_workspace_bytes(*dims)
-        if need:
-            with timing.span("wgrad_f16x3", Ci, Co, k[1], stride, D, H, W, transposed, **span):
-                launch(1, xmeta, dymeta, need)
-            return
-    need = lib.osa_conv3d_wgrad_workspace_bytes(*dims)
-    if need == 0:
-        raise _lib.EngineError("osa_conv3d_wgrad_workspace_bytes: unsupported layer " + str(dims))
+        with timing.span("wgrad_f16x3", Ci, Co, k[1], stride, D, H, W, transposed, **span):
+            if run(1, xmeta, dymeta):
+                return
     if xc.dtype != torch.float32 or dyc.dtype != torch.float32:
-        xs, dys = [t.float() for t in xs], [t.float() for t in dys]
+        xs, dys = [t.float() for t in xs], [t.float() for t in dys]      # (dense tensors: .float() keeps the strides the channel strides refer to)
     with timing.span("wgrad", Ci, Co, k[1], stride, D, H, W, transposed, **span):
-        launch(0, None, None, need)
+        run(0, None, None)
 
 
 # ----------------------------------------------------------------------------- deferred, batched weight gradients (r6)
@@ -827,12 +700,7 @@ def _launch_f16(x, xcs, packed, y, ycs, xdims, Co, k, pad, dil, act, bias):
     geom = [k[0], k[1], k[2], 1, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2]]
     macs = B * y.shape[2] * y.shape[3] * y.shape[4] * Ci * Co * k[0] * k[1] * k[2]
     with timing.span("conv3d", Ci, Co, k[1], 1, D, H, W, flops=2 * macs, nbytes=x.element_size() * B * D * H * W * Ci + y.element_size() * y.numel()):
-        ext = engine._ext.load()
-        if ext is not None:
-            ext.conv_ndhwc(x, 0, packed, scale, bias, None, 0, y, 0, None, dims, geom, 0, 2, act, 0.0, 1.0, [])
-        else:
-            _lib.call("osa_conv3d_ndhwc_f16", x.data_ptr(), packed.data_ptr(), _p(scale), _p(bias), None, y.data_ptr(),
-                      B, D, H, W, Ci, xcs, Co, ycs, 0, k[0], k[1], k[2], 1, pad[0], pad[1], pad[2], dil[0], dil[1], dil[2], None, 0, act, 0.0, _stream())
+        _ext.load().conv_ndhwc(x, 0, packed, scale, bias, None, 0, y, 0, None, dims, geom, 0, 2, act, 0.0, 1.0, [])
 
 
 def _native_f16(x, weight, stride, precision, dilation=1):
@@ -901,13 +769,7 @@ class _ConvTranspose2d(torch.autograd.Function):
             y.zero_()
         Ci4 = (Ci + 3) // 4 * 4
         _defer_note_use(cache, ctx.needs_input_grad[1], w, None, True, None)      # (the k = 4 up-sampling heads run once per GRU iteration: batched weight gradient)
-        if _ext_conv(2, xc, packed, y, [B, 1, H, W, Ci4, Cs, Co, CoS, 0, 0], [k, pad, opad], precision, osc):
-            ctx.save_for_backward(xc, wf)
-            ctx.meta = (pad, opad, precision, x.dtype)
-            return _alias(y[:, :Co, 0])
-        sfx, tail = _sfx_tail(precision, xc, y, osc)
-        _lib.call("osa_deconv2d_nhwc_" + sfx, xc.data_ptr(), packed.data_ptr(), None, None, None, y.data_ptr(),
-                  B, H, W, Ci4, Cs, Co, CoS, 0, k, pad, opad, None, 0, 0, 0.0, *tail)
+        _ext_conv(2, xc, packed, y, [B, 1, H, W, Ci4, Cs, Co, CoS, 0, 0], [k, pad, opad], precision, osc)
         ctx.save_for_backward(xc, wf)
         ctx.meta = (pad, opad, precision, x.dtype)
         return _alias(y[:, :Co, 0])
@@ -1032,7 +894,7 @@ def conv2d_pair(x, weight_a, weight_b, padding=0, dilation=1, precision=None):
 
 # ----------------------------------------------------------------------------- fused ConvGRU gates (training path, csrc/gru_train.hip)
 def _nhwc_ref(t, C):
-    """(tensor to keep alive, _lib.NhwcRef) for a logical [B, >=C, H, W] CUDA tensor read / written as NHWC with a channel stride: engine
+    """`t` as a logical [B, >=C, H, W] CUDA tensor the gate kernels read / write as NHWC with a channel stride (osa_nhwc_ref): engine
     outputs (channel-sliced NDHWC views), channels_last tensors and anything whose strides are (H*W*cs, 1, W*cs, cs) pass as they are;
     other layouts / dtypes are converted once (differentiable torch ops; callers memoise per tensor object where an operand repeats)."""
     memo = getattr(t, "_osa_nhwc", None)            # operands that repeat (the context features cz / cr / cq: the same objects in all 22
@@ -1049,21 +911,16 @@ def _nhwc_ref(t, C):
         t = t.contiguous(memory_format=torch.channels_last)
         if t.shape[1] % 4 or t.stride(1) != 1:          # (C % 4 == 0 is asserted by the callers; size-1 dims can leave ambiguous strides)
             t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-        cs = t.stride(3)
     if t is not src:
         try:
             src._osa_nhwc = (src._version, t)
         except Exception:
             pass
-    return t, _lib.NhwcRef(t.data_ptr(), int(cs), 1 if t.dtype == torch.float16 else 0)
+    return t
 
 
 def _new_nhwc(B, C, H, W, device, dtype):
     return torch.empty((B, H, W, C), device=device, dtype=dtype).permute(0, 3, 1, 2)
-
-
-def _bias_ptr(b):
-    return None if b is None else b.data_ptr()
 
 
 class _GruGatesRZ(torch.autograd.Function):
@@ -1077,14 +934,8 @@ class _GruGatesRZ(torch.autograd.Function):
         bzf, brf = (None if bz is None else _f32c(bz.detach())), (None if br is None else _f32c(br.detach()))
         z = _new_nhwc(B, C, H, W, pre.device, torch.float32)             # internal: only the q kernel reads it
         rh = _new_nhwc(B, C, H, W, pre.device, rh_dtype)
-        ext = engine._ext.load()
-        if ext is not None:
-            ext.gru_gates_rz_fwd(keep[0][0], bzf, brf, keep[1][0], keep[2][0], keep[3][0], z, rh)
-        else:
-            zr, rhr = _nhwc_ref(z, C), _nhwc_ref(rh, C)
-            _lib.call("osa_gru_gates_rz_fwd", keep[0][1], _bias_ptr(bzf), _bias_ptr(brf), keep[1][1], keep[2][1], keep[3][1], zr[1], rhr[1],
-                      B * H * W, C, _stream())
-        ctx.save_for_backward(keep[0][0], keep[1][0], keep[2][0], keep[3][0], *([] if bzf is None else [bzf]), *([] if brf is None else [brf]))
+        _ext.load().gru_gates_rz_fwd(keep[0], bzf, brf, keep[1], keep[2], keep[3], z, rh)
+        ctx.save_for_backward(*keep, *([] if bzf is None else [bzf]), *([] if brf is None else [brf]))
         ctx.has_b = (bzf is not None, brf is not None)
         ctx.dt = (pre.dtype, cz.dtype, cr.dtype, h.dtype, None if bz is None else bz.dtype, None if br is None else br.dtype)
         return z, rh
@@ -1101,12 +952,7 @@ class _GruGatesRZ(torch.autograd.Function):
         refs = [_nhwc_ref(t, n) for t, n in ((pre, C2), (cz, C), (cr, C), (h, C), (dz, C), (drh, C))]
         dpre = _new_nhwc(B, C2, H, W, pre.device, torch.float32)
         dh = _new_nhwc(B, C, H, W, pre.device, torch.float32)
-        ext = engine._ext.load()
-        if ext is not None:
-            ext.gru_gates_rz_bwd(refs[0][0], bzf, brf, refs[1][0], refs[2][0], refs[3][0], refs[4][0], refs[5][0], dpre, dh)
-        else:
-            _lib.call("osa_gru_gates_rz_bwd", refs[0][1], _bias_ptr(bzf), _bias_ptr(brf), refs[1][1], refs[2][1], refs[3][1], refs[4][1], refs[5][1],
-                      _nhwc_ref(dpre, C2)[1], _nhwc_ref(dh, C)[1], B * H * W, C, _stream())
+        _ext.load().gru_gates_rz_bwd(refs[0], bzf, brf, refs[1], refs[2], refs[3], refs[4], refs[5], dpre, dh)
         pdt, czdt, crdt, hdt, bzdt, brdt = ctx.dt
         db = _bias_grad(dpre.unsqueeze(2), C2) if (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]) else None       # one reduction for both biases
         return (dpre.to(pdt), None if bzdt is None or db is None else db[:C].to(bzdt), None if brdt is None or db is None else db[C:].to(brdt),
@@ -1123,12 +969,8 @@ class _GruGatesQ(torch.autograd.Function):
         keep = [_nhwc_ref(t, C) for t in (z, qpre, cq, h)]
         bqf = None if bq is None else _f32c(bq.detach())
         out = _new_nhwc(B, C, H, W, qpre.device, out_dtype)
-        ext = engine._ext.load()
-        if ext is not None:
-            ext.gru_gates_q_fwd(keep[0][0], keep[1][0], bqf, keep[2][0], keep[3][0], out)
-        else:
-            _lib.call("osa_gru_gates_q_fwd", keep[0][1], keep[1][1], _bias_ptr(bqf), keep[2][1], keep[3][1], _nhwc_ref(out, C)[1], B * H * W, C, _stream())
-        ctx.save_for_backward(keep[0][0], keep[1][0], keep[2][0], keep[3][0], *([] if bqf is None else [bqf]))
+        _ext.load().gru_gates_q_fwd(keep[0], keep[1], bqf, keep[2], keep[3], out)
+        ctx.save_for_backward(*keep, *([] if bqf is None else [bqf]))
         ctx.dt = (z.dtype, qpre.dtype, cq.dtype, h.dtype, None if bq is None else bq.dtype)
         return out
 
@@ -1140,12 +982,7 @@ class _GruGatesQ(torch.autograd.Function):
         B, C, H, W = qpre.shape
         refs = [_nhwc_ref(t, C) for t in (z, qpre, cq, h, dout)]
         dz, dq, dh = (_new_nhwc(B, C, H, W, qpre.device, torch.float32) for _ in range(3))
-        ext = engine._ext.load()
-        if ext is not None:
-            ext.gru_gates_q_bwd(refs[0][0], refs[1][0], bqf, refs[2][0], refs[3][0], refs[4][0], dz, dq, dh)
-        else:
-            _lib.call("osa_gru_gates_q_bwd", refs[0][1], refs[1][1], _bias_ptr(bqf), refs[2][1], refs[3][1], refs[4][1],
-                      _nhwc_ref(dz, C)[1], _nhwc_ref(dq, C)[1], _nhwc_ref(dh, C)[1], B * H * W, C, _stream())
+        _ext.load().gru_gates_q_bwd(refs[0], refs[1], bqf, refs[2], refs[3], refs[4], dz, dq, dh)
         zdt, qdt, cqdt, hdt, bqdt = ctx.dt
         return (dz.to(zdt), dq.to(qdt), None if bqdt is None or not ctx.needs_input_grad[2] else _bias_grad(dq.unsqueeze(2), C).to(bqdt),
                 dq.to(cqdt) if ctx.needs_input_grad[3] else None, dh.to(hdt) if ctx.needs_input_grad[4] else None, None)
@@ -1231,14 +1068,7 @@ class _ContextUpsampleLogits(torch.autograd.Function):
     def forward(ctx, disp_low, logits, scale, gain):
         d = _f32c(disp_low)
         lg = logits if logits.dtype in (torch.float16, torch.float32) else logits.float()
-        B, _, h, w = d.shape
-        ext = engine._ext.load()
-        if ext is not None:
-            out = ext.context_upsample_logits(d, lg, scale, gain)
-        else:
-            out = torch.empty((B, h * scale, w * scale), device=d.device, dtype=torch.float32)
-            _lib.call("osa_context_upsample_logits_f32", d.data_ptr(), lg.data_ptr(), int(lg.dtype == torch.float16), (ctypes.c_longlong * 4)(*lg.stride()),
-                      out.data_ptr(), B, h, w, scale, float(gain), _stream())
+        out = _ext.load().context_upsample_logits(d, lg, scale, gain)
         ctx.save_for_backward(d, lg)
         ctx.meta = (scale, gain, disp_low.dtype, logits.dtype)
         return out
@@ -1247,17 +1077,7 @@ class _ContextUpsampleLogits(torch.autograd.Function):
     def backward(ctx, dout):
         d, lg = ctx.saved_tensors
         scale, gain, ddt, ldt = ctx.meta
-        B, _, h, w = d.shape
-        g = _f32c(dout)
-        ext = engine._ext.load()
-        if ext is not None:
-            dd, dl = ext.context_upsample_logits_bwd(d, lg, g, scale, gain)
-        else:
-            dd = torch.empty_like(d)
-            dl = torch.empty(lg.shape, device=lg.device, dtype=lg.dtype)      # contiguous NCHW, as the torch composition's softmax backward returns it
-            sc = torch.empty((B, 9, h, w), device=d.device, dtype=torch.float32)
-            _lib.call("osa_context_upsample_logits_bwd_f32", d.data_ptr(), lg.data_ptr(), int(lg.dtype == torch.float16), (ctypes.c_longlong * 4)(*lg.stride()),
-                      g.data_ptr(), dd.data_ptr(), dl.data_ptr(), (ctypes.c_longlong * 4)(*dl.stride()), sc.data_ptr(), B, h, w, scale, float(gain), _stream())
+        dd, dl = _ext.load().context_upsample_logits_bwd(d, lg, _f32c(dout), scale, gain)
         return (dd.to(ddt) if ctx.needs_input_grad[0] else None), (dl.to(ldt) if ctx.needs_input_grad[1] else None), None, None
 
 

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import _ext, _lib, timing
-from .ops import _stream, _p, empty_cl, is_cl
+from .ops import _stream, empty_cl, is_cl
 
 import math
 import os
@@ -269,12 +269,9 @@ class PackedConv3d:
         gain = (wsum * self.scale.abs()).amax() if self.scale is not None else wsum.amax()
         smax = self.shift.abs().amax() if self.shift is not None else torch.zeros((), device=w.device)
         self.coef = torch.stack([gain.float(), smax.float()]).contiguous()
-        st = _stream()
-        f16 = self.precision == "f16x3"
-        h16 = self.precision == "f16"
         self.out_scale = 1.0
         wscale = 1.0
-        if f16:
+        if self.precision == "f16x3":
             # power-of-two pre-scale: largest |w| lands in [2^13, 2^14) -> hi AND lo parts are fp16 normals
             amax = float(w.abs().max())
             k = 0 if amax == 0.0 or not math.isfinite(amax) else int(math.floor(math.log2(16384.0 / amax)))
@@ -293,17 +290,8 @@ class PackedConv3d:
                 fam = "osa_deconv3d"
             n = getattr(_lib.load(), fam + "_packed_floats")(self.Ci, self.Co, self.k[1])
             self.packed = torch.zeros(n, device=w.device, dtype=torch.float32)
-            ext = _ext.load()
-            if ext is not None:
-                ext.weight_pack(w, self.packed, 2 if self.flat_deconv else 1, PRECISIONS.index(self.precision), [self.Ci, self.Co, self.k[1], self.pad[1]], wscale)
-            elif f16:
-                _lib.call(fam + "_pack_f16x3", w.data_ptr(), self.packed.data_ptr(), self.Ci, self.Co,
-                          self.k[1], self.pad[1], wscale, st)
-            elif h16:
-                _lib.call(fam + "_pack_f16", w.data_ptr(), self.packed.data_ptr(), self.Ci, self.Co, self.k[1], self.pad[1], st)
-            else:
-                _lib.call(fam + "_pack_f32", w.data_ptr(), self.packed.data_ptr(), self.Ci, self.Co,
-                          self.k[1], self.pad[1], st)
+            _ext.load().weight_pack(w, self.packed, 2 if self.flat_deconv else 1, PRECISIONS.index(self.precision),
+                                    [self.Ci, self.Co, self.k[1], self.pad[1]], wscale)
         else:
             self.Co, self.Ci = w.shape[0], w.shape[1]
             assert conv.groups == 1
@@ -311,15 +299,7 @@ class PackedConv3d:
             assert s[1] == s[2] and (s[0] == s[1] or (self.k[0] == 1)), f"anisotropic stride {s}"
             n = _lib.load().osa_conv3d_packed_floats(self.Ci, self.Co, *self.k)
             self.packed = torch.zeros(n, device=w.device, dtype=torch.float32)
-            ext = _ext.load()
-            if ext is not None:
-                ext.weight_pack(w, self.packed, 0, PRECISIONS.index(self.precision), [self.Ci, self.Co, *self.k], wscale)
-            elif f16:
-                _lib.call("osa_conv3d_pack_f16x3", w.data_ptr(), self.packed.data_ptr(), self.Ci, self.Co, *self.k, wscale, st)
-            elif h16:
-                _lib.call("osa_conv3d_pack_f16", w.data_ptr(), self.packed.data_ptr(), self.Ci, self.Co, *self.k, st)
-            else:
-                _lib.call("osa_conv3d_pack_f32", w.data_ptr(), self.packed.data_ptr(), self.Ci, self.Co, *self.k, st)
+            _ext.load().weight_pack(w, self.packed, 0, PRECISIONS.index(self.precision), [self.Ci, self.Co, *self.k], wscale)
 
     def out_shape(self, D, H, W):
         if self.transposed:
@@ -373,11 +353,6 @@ class PackedConv3d:
             assert gate.is_contiguous() and tuple(gate.shape[:3]) == (B, Ho, Wo) and gate.shape[3] >= self.Co
             assert h16 or gate.dtype == torch.float32
             gCs = gate.shape[3]
-        ext = _ext.load()
-        xp = yp = rp = None                                  # raw addresses: the ctypes path only (FakeTensors have none: tests/test_gpu_fake_trace.py)
-        if ext is None:
-            xp, yp = x.data_ptr() + x.element_size() * x_off, out.data_ptr() + out.element_size() * out_off
-            rp = None if residual is None else residual.data_ptr() + residual.element_size() * res_off
         act = self.act | (GATE_RAW if (gate is not None and gate_raw) else 0)
         if gate_channels:
             assert gate is not None and gate_channels % 4 == 0 and 0 < gate_channels <= self.Co
@@ -399,78 +374,40 @@ class PackedConv3d:
             assert not (fmt & RES_SPLIT) or res_off % 16 == 0
             assert not out_split or (self.Co % 16 == 0 and yCs % 16 == 0 and out_off % 16 == 0)
             act |= fmt
-        rng, st = None, _stream()
+        metas = []
         if self.precision == "f16x3":
             # operand ranges (device-side): scale of x / residual / redir input, bound for a split output, and the
-            # output's own running maximum
+            # output's own running maximum (osa_f16x3_ranges: x, residual, redir, y, bound_coef, redir_bound_coef, weight_scale)
             need_res = residual is not None and (out_split or is_split(residual))    # its scale (split) / its share of the output bound
-            mx, mr, mo = input_meta(x), (input_meta(residual) if need_res else None), attach_meta(out, st)
-            mrd = None if redir is None else input_meta(redir[1])
-            if ext is None:
-                rng = _lib.F16x3Ranges(mx.data_ptr(), None if mr is None else mr.data_ptr(),
-                                       None if mrd is None else mrd.data_ptr(), mo.data_ptr(),
-                                       self.coef.data_ptr(), None if redir is None else redir[0].coef.data_ptr())
+            e = _empty(x.device)
+            mx, mr, mo = input_meta(x), (input_meta(residual) if need_res else e), attach_meta(out, _stream())
+            if redir is None:
+                metas = [mx, mr, e, mo, self.coef, e, e]
+            else:
+                metas = [mx, e, input_meta(redir[1]), mo, self.coef, redir[0].coef, e]
         taps = self.k[0] * self.k[1] * self.k[2]
         macs = B * Do * Ho * Wo * self.Ci * self.Co * taps / ((4 if self.flat_deconv else 8) if self.transposed else 1)
         nbytes = 4 * B * (D * H * W * self.Ci + Do * Ho * Wo * self.Co * (1 + (residual is not None) + (redir is not None)))
         with timing.span("deconv3d" if self.transposed else "conv3d", self.Ci, self.Co, self.k[0], self.stride[1], D, H, W,
                          flops=2 * macs, nbytes=nbytes):
-            tail = (self.out_scale, rng, st) if self.precision == "f16x3" else (st,)
-            sfx = self.precision
-            if ext is not None and redir is not None:
+            # csrc/torch_ext.cpp: one dispatcher call, tensors in, current HIP stream inside
+            if redir is not None:
                 assert not h16, "the f16 mode has no fused redir branch (run the 1x1x1 layer and pass it as residual)"
                 rl, rt = redir
                 assert self.transposed and not self.flat_deconv and residual is None and gate is None
                 assert rl.precision == self.precision and rl.k == (1, 1, 1) and rl.Co == self.Co and rl.act == ACT_NONE
                 assert is_cl(rt) and tuple(rt.shape[2:]) == (Do, Ho, Wo) and rt.shape[1] >= rl.Ci and rl.Ci <= 64
-                if self.precision == "f16x3":
-                    e = _empty(x.device)
-                    metas = [mx, e, mrd, mo, self.coef, rl.coef, e]
-                else:
-                    metas = []
-                ext.deconv_redir(x, x_off, self.packed, self.scale, self.shift, out, out_off, [B, D, H, W, Ci, Cs, self.Co, yCs],
-                                 [self.k[0], self.pad[0], self.opad[0]], rt, [rt.shape[1], (rl.Ci + 3) // 4 * 4], rl.packed, rl.scale, rl.shift,
-                                 rl.out_scale, PRECISIONS.index(self.precision), act, self.slope, self.out_scale, metas)
-            elif ext is not None:
-                # PyTorch-ROCm C++ extension (csrc/torch_ext.cpp): one dispatcher call, tensors in, current HIP stream inside
+                _ext.load().deconv_redir(x, x_off, self.packed, self.scale, self.shift, out, out_off, [B, D, H, W, Ci, Cs, self.Co, yCs],
+                                         [self.k[0], self.pad[0], self.opad[0]], rt, [rt.shape[1], (rl.Ci + 3) // 4 * 4], rl.packed, rl.scale,
+                                         rl.shift, rl.out_scale, PRECISIONS.index(self.precision), act, self.slope, self.out_scale, metas)
+            else:
                 if self.transposed:
                     fam, geom = (2 if self.flat_deconv else 1), [self.k[1], self.pad[1], self.opad[1]]
                 else:
                     fam, geom = 0, [self.k[0], self.k[1], self.k[2], self.stride[1], self.pad[0], self.pad[1], self.pad[2], self.dil[0], self.dil[1], self.dil[2]]
-                if self.precision == "f16x3":
-                    e = _empty(x.device)
-                    metas = [mx, e if mr is None else mr, e, mo, self.coef, e, e]
-                else:
-                    metas = []
-                ext.conv_ndhwc(x, x_off, self.packed, self.scale, self.shift, residual, res_off, out, out_off, gate,
-                               [B, D, H, W, Ci, Cs, self.Co, yCs, rCs, gCs], geom, fam, PRECISIONS.index(self.precision), act, self.slope,
-                               self.out_scale, metas)
-            elif redir is not None:
-                assert not h16, "the f16 mode has no fused redir branch (run the 1x1x1 layer and pass it as residual)"
-                rl, rt = redir
-                assert self.transposed and not self.flat_deconv and residual is None and gate is None
-                assert rl.precision == self.precision and rl.k == (1, 1, 1) and rl.Co == self.Co and rl.act == ACT_NONE
-                assert is_cl(rt) and tuple(rt.shape[2:]) == (Do, Ho, Wo) and rt.shape[1] >= rl.Ci and rl.Ci <= 64
-                rtail = (rl.out_scale,) if self.precision == "f16x3" else ()
-                _lib.call("osa_deconv3d_redir_ndhwc_" + sfx, xp, self.packed.data_ptr(), _p(self.scale), _p(self.shift),
-                          yp, B, D, H, W, Ci, Cs, self.Co, yCs, self.k[0], self.pad[0], self.opad[0],
-                          rt.data_ptr(), rt.shape[1], (rl.Ci + 3) // 4 * 4, rl.packed.data_ptr(), _p(rl.scale), _p(rl.shift), *rtail,
-                          act, self.slope, *tail)
-            elif self.flat_deconv:
-                assert D == 1
-                _lib.call("osa_deconv2d_nhwc_" + sfx, xp, self.packed.data_ptr(), _p(self.scale), _p(self.shift),
-                          rp, yp, B, H, W, Ci, Cs, self.Co, yCs, rCs,
-                          self.k[1], self.pad[1], self.opad[1], _p(gate), gCs, act, self.slope, *tail)
-            elif self.transposed:
-                _lib.call("osa_deconv3d_ndhwc_" + sfx, xp, self.packed.data_ptr(), _p(self.scale), _p(self.shift),
-                          rp, yp, B, D, H, W, Ci, Cs, self.Co, yCs, rCs,
-                          self.k[0], self.pad[0], self.opad[0], _p(gate), gCs, act, self.slope, *tail)
-            else:
-                _lib.call("osa_conv3d_ndhwc_" + sfx, xp, self.packed.data_ptr(), _p(self.scale), _p(self.shift),
-                          rp, yp, B, D, H, W, Ci, Cs, self.Co, yCs, rCs,
-                          self.k[0], self.k[1], self.k[2], self.stride[1],
-                          self.pad[0], self.pad[1], self.pad[2], self.dil[0], self.dil[1], self.dil[2],
-                          _p(gate), gCs, act, self.slope, *tail)
+                _ext.load().conv_ndhwc(x, x_off, self.packed, self.scale, self.shift, residual, res_off, out, out_off, gate,
+                                       [B, D, H, W, Ci, Cs, self.Co, yCs, rCs, gCs], geom, fam, PRECISIONS.index(self.precision), act, self.slope,
+                                       self.out_scale, metas)
         if out_split and not h16:
             out._osa_split = True
         return out
@@ -500,11 +437,7 @@ class DepthwiseConv2d:
             else:
                 self.shift = (self.shift + bias * self.scale).contiguous()
         self.packed = torch.empty(self.k[0] * self.k[1] * self.C, device=w.device, dtype=torch.float32)
-        ext = _ext.load()
-        if ext is not None:
-            ext.weight_pack(w, self.packed, 3, 0, [self.C, self.k[0], self.k[1]], 1.0)
-        else:
-            _lib.call("osa_dwconv2d_pack_f32", w.data_ptr(), self.packed.data_ptr(), self.C, self.k[0], self.k[1], _stream())
+        _ext.load().weight_pack(w, self.packed, 3, 0, [self.C, self.k[0], self.k[1]], 1.0)
 
     def __call__(self, x, add=None, out_f16=False):
         """out_f16 / an fp16 `x` (r6, the 3 x 3 layers in the f16 mode): the chain tensors between MobileV2Residual's expansion, depthwise and
@@ -523,23 +456,12 @@ class DepthwiseConv2d:
             assert is_cl(add) and tuple(add.shape[2:]) == (1, Ho, Wo) and add.shape[1] >= self.C
             aCs = add.shape[1]
         with timing.span("dwconv2d", self.C, self.C, self.k[0] * self.k[1], self.stride[0], 1, H, W):
-            ext = _ext.load()
             if h16:
-                if ext is not None:
-                    ext.dwconv2d_f16io(x, self.packed, self.scale, self.shift, out, [B, H, W, self.C, Cs, self.C],
-                                       [self.k[0], self.k[1], self.stride[0], self.pad[0], self.pad[1]], self.act, attach_meta(out))
-                else:
-                    _lib.call("osa_dwconv2d_nhwc_f16io", x.data_ptr(), int(x.dtype == torch.float16), self.packed.data_ptr(), _p(self.scale), _p(self.shift),
-                              out.data_ptr(), int(out_f16), B, H, W, self.C, Cs, self.C, self.k[0], self.k[1], self.stride[0], self.pad[0], self.pad[1],
-                              self.act, attach_meta(out).data_ptr(), _stream())
-            elif ext is not None:
-                ext.dwconv2d(x, self.packed, self.scale, self.shift, add, out, [B, H, W, self.C, Cs, self.C, aCs],
-                             [self.k[0], self.k[1], self.stride[0], self.pad[0], self.pad[1], self.dil[0], self.dil[1]], self.act, attach_meta(out))
+                _ext.load().dwconv2d_f16io(x, self.packed, self.scale, self.shift, out, [B, H, W, self.C, Cs, self.C],
+                                           [self.k[0], self.k[1], self.stride[0], self.pad[0], self.pad[1]], self.act, attach_meta(out))
             else:
-                _lib.call("osa_dwconv2d_nhwc_f32", x.data_ptr(), self.packed.data_ptr(), _p(self.scale), _p(self.shift),
-                          _p(add), out.data_ptr(), B, H, W, self.C, Cs, self.C, aCs,
-                          self.k[0], self.k[1], self.stride[0], self.pad[0], self.pad[1], self.dil[0], self.dil[1],
-                          self.act, attach_meta(out).data_ptr(), _stream())
+                _ext.load().dwconv2d(x, self.packed, self.scale, self.shift, add, out, [B, H, W, self.C, Cs, self.C, aCs],
+                                     [self.k[0], self.k[1], self.stride[0], self.pad[0], self.pad[1], self.dil[0], self.dil[1]], self.act, attach_meta(out))
         return out
 
 
@@ -560,11 +482,7 @@ class SmallCoConv3d:
         self.packed = torch.empty(n + 16, device=self.w.device, dtype=torch.float32)     # scalar-cache friendly layout
         off = (-self.packed.data_ptr() // 4) % 16                                         # 64-byte alignment
         self.packed = self.packed[off:off + n]
-        ext = _ext.load()
-        if ext is not None:
-            ext.weight_pack(self.w, self.packed, 4, 0, [self.Ci, self.Co, *self.k], 1.0)
-        else:
-            _lib.call("osa_conv3d_small_co_pack_f32", self.w.data_ptr(), self.packed.data_ptr(), self.Ci, self.Co, *self.k, _stream())
+        _ext.load().weight_pack(self.w, self.packed, 4, 0, [self.Ci, self.Co, *self.k], 1.0)
 
     def __call__(self, x, residual=None):
         """x NDHWC logical [B,Cs,D,H,W] -> logical [B,Co,D,H,W] stored [B,D,H,W,Co] (for Co==1 this
@@ -575,10 +493,5 @@ class SmallCoConv3d:
         if residual is not None:
             assert tuple(residual.shape) == (B, self.Co, D, H, W) and is_cl(residual)
         with timing.span("conv3d_small_co", self.Ci, self.Co, self.k[0], 1, D, H, W):
-            ext = _ext.load()
-            if ext is not None:
-                ext.small_co_conv(x, self.packed, self.bias, residual, y, [B, D, H, W, self.Ci, Cs, self.Co, self.Co], [*self.k, *self.pad])
-            else:
-                _lib.call("osa_conv3d_small_co_packed_ndhwc_f32", x.data_ptr(), self.packed.data_ptr(), _p(self.bias), _p(residual), y.data_ptr(),
-                          B, D, H, W, self.Ci, Cs, self.Co, self.Co, *self.k, *self.pad, _stream())
+            _ext.load().small_co_conv(x, self.packed, self.bias, residual, y, [B, D, H, W, self.Ci, Cs, self.Co, self.Co], [*self.k, *self.pad])
         return y.permute(0, 4, 1, 2, 3)

@@ -8,12 +8,10 @@ iteration produces the reference's [B,(C+1)*(2r+1)*levels,H,W] tensor (replacing
 calls, their coordinate tensors and the concatenations)."""
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from . import _ext, _lib, ops, timing
-from .ops import _f32c, _stream, is_cl
+from . import _ext, ops, timing
+from .ops import _f32c, is_cl
 
 
 import os
@@ -61,54 +59,27 @@ class _Lookup(torch.autograd.Function):
         d, cx, levels = _f32c(d), _f32c(cx), tuple(_f32c(t) for t in levels)
         ctx.state = state
         L = len(levels) // 2
-        geo, corr = levels[:L], levels[L:]
         B, H, W = d.shape
         out = torch.empty((B, (C + 1) * (2 * radius + 1) * L, H, W), device=d.device, dtype=torch.float32)
-        ext = _ext.load()
-        if ext is not None:                               # PyTorch-ROCm C++ extension: the pyramid as a tensor list
-            ext.geo_lookup(list(levels), d, cx, out, C, radius)
-            ctx.save_for_backward(d, cx)
-            ctx.meta = (C, radius, L, [tuple(t.shape) for t in levels])
-            return out
-        gp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in geo])
-        cp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in corr])
-        gl = (ctypes.c_int * L)(*[t.shape[-1] for t in geo])
-        cl = (ctypes.c_int * L)(*[t.shape[-1] for t in corr])
-        _lib.call("osa_geo_lookup_f32", gp, cp, gl, cl, L, d.data_ptr(), cx.data_ptr(), out.data_ptr(), B, H, W, C, radius, _stream())
+        _ext.load().geo_lookup(list(levels), d, cx, out, C, radius)       # the pyramid as a tensor list: geo levels, then corr levels
         ctx.save_for_backward(d, cx)
-        ctx.meta = (C, radius, L, [tuple(t.shape) for t in levels])
+        ctx.meta = (C, radius, [tuple(t.shape) for t in levels])
         return out
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, dout):
         d, cx = ctx.saved_tensors
-        C, radius, L, shapes = ctx.meta
-        B, H, W = d.shape
-        ext = _ext.load()
+        C, radius, shapes = ctx.meta
         st = ctx.state
         if st is not None:
             # accumulate into the pyramid's gradient buffers; _LevelJoin delivers them (r6)
             if st.acc is None:
                 st.acc = [torch.zeros(s, device=d.device, dtype=torch.float32) for s in shapes]
-            acc = st.acc
-            if ext is not None:
-                ext.geo_lookup_bwd_acc(acc, d, cx, _f32c(dout), C, radius)
-            else:
-                _lib.call("osa_geo_lookup_bwd_acc_f32", (ctypes.c_void_p * L)(*[t.data_ptr() for t in acc[:L]]), (ctypes.c_void_p * L)(*[t.data_ptr() for t in acc[L:]]),
-                          (ctypes.c_int * L)(*[s[-1] for s in shapes[:L]]), (ctypes.c_int * L)(*[s[-1] for s in shapes[L:]]), L,
-                          d.data_ptr(), cx.data_ptr(), _f32c(dout).data_ptr(), B, H, W, C, radius, _stream())
+            _ext.load().geo_lookup_bwd_acc(st.acc, d, cx, _f32c(dout), C, radius)
             return (None, None, None, None, None, *([None] * len(shapes)))
         grads = [torch.empty(s, device=d.device, dtype=torch.float32) for s in shapes]
-        if ext is not None:
-            ext.geo_lookup_bwd(grads, d, cx, _f32c(dout), C, radius)
-            return (None, None, None, None, None, *grads)
-        gp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in grads[:L]])
-        cp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in grads[L:]])
-        gl = (ctypes.c_int * L)(*[s[-1] for s in shapes[:L]])
-        cl = (ctypes.c_int * L)(*[s[-1] for s in shapes[L:]])
-        _lib.call("osa_geo_lookup_bwd_f32", gp, cp, gl, cl, L, d.data_ptr(), cx.data_ptr(), _f32c(dout).data_ptr(),
-                  B, H, W, C, radius, _stream())
+        _ext.load().geo_lookup_bwd(grads, d, cx, _f32c(dout), C, radius)
         return (None, None, None, None, None, *grads)
 
 
@@ -147,41 +118,26 @@ class CombinedGeoEncodingVolume:
             self.meta[0:1] = torch.maximum(rows.detach().abs().amax(), corr.detach().abs().amax()).reshape(1)
             return
         f1, f2 = _f32c(init_fmap1), _f32c(init_fmap2)
-        B, Cf, H, W1 = f1.shape
+        B, _, H, W1 = f1.shape
         W2 = f2.shape[3]
         dev = f1.device
         corr = torch.empty((B, H, W1, W2), device=dev, dtype=torch.float32)
         ext = _ext.load()
-        if ext is not None:
-            ext.allpairs_corr(f1, f2, corr)
-        else:
-            _lib.call("osa_allpairs_corr_f32", f1.data_ptr(), f2.data_ptr(), corr.data_ptr(), B, Cf, H, W1, W2, _stream())
+        ext.allpairs_corr(f1, f2, corr)
         gv = geo_volume if is_cl(geo_volume) and geo_volume.dtype == torch.float32 else ops.to_cl(geo_volume.float(), pad_to=1)
         _, Cs, D, Hg, Wg = gv.shape
         C = geo_volume.shape[1] if not is_cl(geo_volume) else Cs
         self.C = C
         assert (Hg, Wg) == (H, W1)
         rows = torch.empty((B, H, W1, C, D), device=dev, dtype=torch.float32)
-        if ext is not None:
-            ext.geo_rows(gv, rows, C)
-        else:
-            _lib.call("osa_geo_rows_f32", gv.data_ptr(), rows.data_ptr(), B, D, H, W1, C, Cs, _stream())
+        ext.geo_rows(gv, rows, C)
         self.geo_volume_pyramid, self.init_corr_pyramid = [rows], [corr]
         for _ in range(num_levels - 1):
             g, c = self.geo_volume_pyramid[-1], self.init_corr_pyramid[-1]
             g2 = torch.empty(g.shape[:-1] + (g.shape[-1] // 2,), device=dev, dtype=torch.float32)
             c2 = torch.empty(c.shape[:-1] + (c.shape[-1] // 2,), device=dev, dtype=torch.float32)
-            if ext is not None:
-                ext.avgpool_rows(g, g2); ext.avgpool_rows(c, c2)
-            else:
-                _lib.call("osa_avgpool_rows_f32", g.data_ptr(), g2.data_ptr(), g.numel() // g.shape[-1], g.shape[-1], _stream())
-                _lib.call("osa_avgpool_rows_f32", c.data_ptr(), c2.data_ptr(), c.numel() // c.shape[-1], c.shape[-1], _stream())
+            ext.avgpool_rows(g, g2); ext.avgpool_rows(c, c2)
             self.geo_volume_pyramid.append(g2); self.init_corr_pyramid.append(c2)
-        L = num_levels
-        self._gp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.geo_volume_pyramid])
-        self._cp = (ctypes.c_void_p * L)(*[t.data_ptr() for t in self.init_corr_pyramid])
-        self._gl = (ctypes.c_int * L)(*[t.shape[-1] for t in self.geo_volume_pyramid])
-        self._cl = (ctypes.c_int * L)(*[t.shape[-1] for t in self.init_corr_pyramid])
         self.shape = (B, H, W1)
         # range block of every lookup result (f16x3 consumers): taps are convex combinations of volume entries or zero,
         # the coarser pyramid levels are averages -> bounded by max |level 0|; measured once here, not once per iteration
@@ -198,8 +154,7 @@ class CombinedGeoEncodingVolume:
             return _Lookup.apply(d.detach(), cx.detach(), self.C, self.radius, self._acc, *self.geo_volume_pyramid, *self.init_corr_pyramid)
         out = torch.empty((B, (self.C + 1) * (2 * self.radius + 1) * self.num_levels, H, W), device=d.device, dtype=torch.float32)
         with timing.span("geo_lookup", self.C, self.num_levels, self.radius, H, W):
-            _lib.call("osa_geo_lookup_f32", self._gp, self._cp, self._gl, self._cl, self.num_levels,
-                      d.data_ptr(), cx.data_ptr(), out.data_ptr(), B, H, W, self.C, self.radius, _stream())
+            _ext.load().geo_lookup(self.geo_volume_pyramid + self.init_corr_pyramid, d, cx, out, self.C, self.radius)
         return out
 
     def lookup_cl(self, disp, coords):
@@ -213,12 +168,7 @@ class CombinedGeoEncodingVolume:
         d, cx = _f32c(disp), _f32c(coords)
         assert d.numel() == B * H * W and cx.numel() == B * H * W
         with timing.span("geo_lookup", self.C, self.num_levels, self.radius, H, W):
-            ext = _ext.load()
-            if ext is not None:
-                ext.geo_lookup_nhwc(self.geo_volume_pyramid + self.init_corr_pyramid, d, cx, out, out.shape[1], [B, H, W], self.C, self.radius)
-            else:
-                _lib.call("osa_geo_lookup_nhwc_f32", self._gp, self._cp, self._gl, self._cl, self.num_levels,
-                          d.data_ptr(), cx.data_ptr(), out.data_ptr(), out.shape[1], B, H, W, self.C, self.radius, _stream())
+            _ext.load().geo_lookup_nhwc(self.geo_volume_pyramid + self.init_corr_pyramid, d, cx, out, out.shape[1], [B, H, W], self.C, self.radius)
         out._osa_meta = self.meta                  # taps interpolate / zero-pad the volumes: bounded by their max |.|
         return out
 
@@ -226,14 +176,9 @@ class CombinedGeoEncodingVolume:
     def corr(fmap1, fmap2):
         """einsum('aijk,aijh->ajkh') -> [B,H,W1,1,W2] (gru_blocks.py:221-229)."""
         f1, f2 = _f32c(fmap1), _f32c(fmap2)
-        B, Cf, H, W1 = f1.shape
-        W2 = f2.shape[3]
-        out = torch.empty((B, H, W1, 1, W2), device=f1.device, dtype=torch.float32)
-        ext = _ext.load()
-        if ext is not None:
-            ext.allpairs_corr(f1, f2, out)
-        else:
-            _lib.call("osa_allpairs_corr_f32", f1.data_ptr(), f2.data_ptr(), out.data_ptr(), B, Cf, H, W1, W2, _stream())
+        B, _, H, W1 = f1.shape
+        out = torch.empty((B, H, W1, 1, f2.shape[3]), device=f1.device, dtype=torch.float32)
+        _ext.load().allpairs_corr(f1, f2, out)
         return out
 
 

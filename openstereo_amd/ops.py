@@ -21,7 +21,7 @@ from __future__ import annotations
 import torch
 
 from . import _ext, _lib, timing
-from .ranges import attach_meta
+from .ranges import attach_meta, new_meta
 
 NCDHW, NDHWC = 0, 1
 
@@ -51,10 +51,6 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32:
         t = t.float()
     return t if t.is_contiguous() else t.contiguous()
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 def _sum_dtype(*ts):
@@ -90,11 +86,7 @@ def to_cl(x: torch.Tensor, pad_to: int = 4) -> torch.Tensor:
     y = empty_cl(B, Cp, D, H, W, x.device)
     if Cp != Cn:
         y.zero_()
-    ext = _ext.load()
-    if ext is not None:
-        ext.to_cl(xs, y, Cn, D * H * W, 0)
-    else:
-        _lib.call("osa_ncdhw_to_ndhwc_f32", xs.data_ptr(), y.data_ptr(), B, Cn, D * H * W, Cp, 0, _stream())
+    _ext.load().to_cl(xs, y, Cn, D * H * W, 0)
     return y
 
 
@@ -109,11 +101,7 @@ def to_ncdhw(x: torch.Tensor, channels: int | None = None) -> torch.Tensor:
     B, Cs, D, H, W = x.shape
     Cn = Cs if channels is None else channels
     y = torch.empty((B, Cn, D, H, W), device=x.device, dtype=torch.float32)
-    ext = _ext.load()
-    if ext is not None:
-        ext.to_ncdhw(x, y, Cn, D * H * W, 0)
-    else:
-        _lib.call("osa_ndhwc_to_ncdhw_f32", x.data_ptr(), y.data_ptr(), B, Cn, D * H * W, Cs, 0, _stream())
+    _ext.load().to_ncdhw(x, y, Cn, D * H * W, 0)
     return y
 
 
@@ -134,12 +122,7 @@ def _build(lg, rg, G, lc, rc, maxdisp, layout, mask_left=True, out=None, vol_cha
             out = torch.empty((B, VC, maxdisp, H, W), device=ref.device, dtype=torch.float32)
     meta = attach_meta(out) if layout == NDHWC else None     # range block for f16x3 consumers
     with timing.span("build_volume", Cg, G, Cc, layout, maxdisp, H, W):
-        ext = _ext.load()
-        if ext is not None:
-            ext.build_volume(lg, rg, G, lc, rc, out, layout, VC, c_off, maxdisp, bool(mask_left), meta)
-        else:
-            _lib.call("osa_build_volume_f32", _p(lg), _p(rg), Cg, G, _p(lc), _p(rc), Cc,
-                      out.data_ptr(), layout, VC, c_off, B, H, W, maxdisp, 1 if mask_left else 0, _p(meta), _stream())
+        _ext.load().build_volume(lg, rg, G, lc, rc, out, layout, VC, c_off, maxdisp, bool(mask_left), meta)
     return out
 
 
@@ -162,14 +145,7 @@ def build_concat_volume(refimg_fea, targetimg_fea, maxdisp, mask_left=True):
 def correlation_volume(left_feature, right_feature, max_disp):
     """cost_volume.py:32-41 -> [B, max_disp, H, W] (mean over all channels)."""
     _chk(left_feature, "left_feature", 4); _chk(right_feature, "right_feature", 4)
-    l, r = _f32c(left_feature), _f32c(right_feature)
-    B, Cn, H, W = l.shape
-    ext = _ext.load()
-    if ext is not None:
-        out = ext.corr_volume(l, r, int(max_disp))
-    else:
-        out = torch.empty((B, max_disp, H, W), device=l.device, dtype=torch.float32)
-        _lib.call("osa_corr_volume_f32", l.data_ptr(), r.data_ptr(), out.data_ptr(), B, Cn, H, W, max_disp, _stream())
+    out = _ext.load().corr_volume(_f32c(left_feature), _f32c(right_feature), int(max_disp))
     return out if left_feature.dtype == torch.float32 else out.to(left_feature.dtype)
 
 
@@ -194,11 +170,7 @@ def cat_fms(reference_fm, target_fm, max_disp=192, start_disp=0, dilation=1):
     n = (max_disp + dilation - 1) // dilation                                          # psmnet_cost_processor.py:31-33
     idx = torch.tensor([int(i) for i in torch.linspace(start_disp, start_disp + max_disp - 1, n)], dtype=torch.int32, device=ref.device)
     out = torch.empty((B, 2 * C, n, H, W), device=ref.device, dtype=torch.float32)
-    ext = _ext.load()
-    if ext is not None:
-        ext.cat_fms(ref, tgt, out, idx)
-    else:
-        _lib.call("osa_cat_fms_f32", ref.data_ptr(), tgt.data_ptr(), out.data_ptr(), idx.data_ptr(), B, C, H, W, n, _stream())
+    _ext.load().cat_fms(ref, tgt, out, idx)
     return out
 
 
@@ -208,11 +180,7 @@ def _pair_volume(left, right, planes, mode, groups=1):
     B, C, H, W = l.shape
     shape = (B, groups, planes, H, W) if mode == 0 else ((B, planes, H, W) if mode == 3 else (B, C, planes, H, W))
     out = torch.empty(shape, device=l.device, dtype=torch.float32)
-    ext = _ext.load()
-    if ext is not None:
-        ext.pair_volume(l, r, out, groups, planes, mode)
-    else:
-        _lib.call("osa_pair_volume_f32", l.data_ptr(), r.data_ptr(), out.data_ptr(), B, C, groups, H, W, planes, mode, _stream())
+    _ext.load().pair_volume(l, r, out, groups, planes, mode)
     return out if left.dtype == torch.float32 else out.to(left.dtype)
 
 
@@ -269,46 +237,19 @@ def build_cost_volume_from_cl(gwc_feat, num_groups, cat_feat, B, maxdisp, gwc_ch
     assert is_cl(gwc_feat) and gwc_feat.shape[0] == 2 * B and gwc_feat.shape[2] == 1
     _, Gs, _, H, W = gwc_feat.shape
     C = Gs - gwc_off if gwc_channels is None else gwc_channels
-    img = H * W * Gs * 4
-    Cc = cs = 0
+    Cc = 0
     if cat_feat is not None:
         assert is_cl(cat_feat) and cat_feat.shape[0] == 2 * B and tuple(cat_feat.shape[3:]) == (H, W)
-        cs = cat_feat.shape[1]
-        Cc = cs if cat_channels is None else cat_channels
-    nch = num_groups + 2 * Cc
-    VC = (nch + 3) // 4 * 4
+        Cc = cat_feat.shape[1] if cat_channels is None else cat_channels
     gm = getattr(gwc_feat, "_osa_meta", None) if C > 0 else None
     cm = getattr(cat_feat, "_osa_meta", None) if (cat_feat is not None and Cc > 0) else None
-    ext = _ext.load()
-    if ext is not None and gwc_feat.dtype == torch.float32 and (cat_feat is None or cat_feat.dtype == torch.float32):
-        # PyTorch-ROCm C++ extension (csrc/torch_ext.cpp cost_volume_cl): allocation, eligibility check and launch in one dispatcher call
-        from .ranges import new_meta
-        om = new_meta(gwc_feat.device)
-        with timing.span("build_volume", C, num_groups, Cc, NDHWC, maxdisp, H, W):
-            out, split = ext.cost_volume_cl(gwc_feat, cat_feat, B, num_groups, maxdisp, C, Cc, gwc_off, bool(mask_left), bool(out_split), gm, cm, om)
-        out._osa_meta = om
-        if split:
-            out._osa_split = True
-        return out
-    # ctypes path: raw addresses
-    lg, rg = gwc_feat.data_ptr() + 4 * gwc_off, gwc_feat.data_ptr() + 4 * gwc_off + B * img
-    lc = rc = None
-    if cat_feat is not None:
-        lc, rc = cat_feat.data_ptr(), cat_feat.data_ptr() + B * H * W * cs * 4
-    out = empty_cl(B, VC, maxdisp, H, W, gwc_feat.device)
-    if VC != nch:
-        out.zero_()
-    split = bool(out_split) and VC == nch and (C == 0 or gm is not None) and (Cc == 0 or cm is not None) and \
-        _lib.load().osa_build_volume_nhwc_split_eligible(lc, rc, out.data_ptr(), C, num_groups, Gs, Cc, cs, VC, 0, W, maxdisp) == 1
+    om = new_meta(gwc_feat.device)
     with timing.span("build_volume", C, num_groups, Cc, NDHWC, maxdisp, H, W):
-        if split:
-            _lib.call("osa_build_volume_nhwc_split_f16x3", lg, rg, C, num_groups, Gs, lc, rc, Cc, cs, out.data_ptr(), VC, 0,
-                      B, H, W, maxdisp, 1 if mask_left else 0, None if gm is None else gm.data_ptr(), None if cm is None else cm.data_ptr(),
-                      attach_meta(out).data_ptr(), _stream())
-            out._osa_split = True
-        else:
-            _lib.call("osa_build_volume_nhwc_f32", lg, rg, C, num_groups, Gs, lc, rc, Cc, cs, out.data_ptr(), VC, 0,
-                      B, H, W, maxdisp, 1 if mask_left else 0, attach_meta(out).data_ptr(), _stream())
+        # csrc/torch_ext.cpp cost_volume_cl: allocation, eligibility check and launch in one dispatcher call
+        out, split = _ext.load().cost_volume_cl(gwc_feat, cat_feat, B, num_groups, maxdisp, C, Cc, gwc_off, bool(mask_left), bool(out_split), gm, cm, om)
+    out._osa_meta = om
+    if split:
+        out._osa_split = True
     return out
 
 
@@ -317,15 +258,9 @@ def disparity_regression(x, maxdisp, keepdim=True):
     """disp_regression.py:8-12 (keepdim=True) / gwcnet_disp_processor.py:22-26 (keepdim=False)."""
     assert len(x.shape) == 4                                      # disp_regression.py:9
     _chk(x, "x")
-    B, D, H, W = x.shape
+    D = x.shape[1]
     assert D == maxdisp, f"x has {D} disparity planes, maxdisp={maxdisp}"
-    xs = _f32c(x)
-    ext = _ext.load()
-    if ext is not None:                                           # torch extension: at::Tensor in / out (csrc/torch_ext.cpp)
-        out = ext.softargmin(xs)
-    else:
-        out = torch.empty((B, H, W), device=x.device, dtype=torch.float32)
-        _lib.call("osa_softargmin_f32", xs.data_ptr(), out.data_ptr(), B, D, H, W, _stream())
+    out = _ext.load().softargmin(_f32c(x))
     out = out if _sum_dtype(x) == torch.float32 else out.to(x.dtype)
     return out.unsqueeze(1) if keepdim else out
 
@@ -334,17 +269,9 @@ def softmax_disparity_regression(cost, maxdisp=None, keepdim=True, return_prob=F
     """F.softmax(cost, dim=1) + disparity_regression in one kernel (stereobase_gru.py:163-164)."""
     assert len(cost.shape) == 4
     _chk(cost, "cost")
-    B, D, H, W = cost.shape
     if maxdisp is not None:
-        assert D == maxdisp
-    cs = _f32c(cost)
-    ext = _ext.load()
-    if ext is not None:
-        out, prob = ext.softmax_softargmin(cs, bool(return_prob))
-    else:
-        out = torch.empty((B, H, W), device=cost.device, dtype=torch.float32)
-        prob = torch.empty_like(cs) if return_prob else None
-        _lib.call("osa_softmax_softargmin_f32", cs.data_ptr(), _p(prob), out.data_ptr(), B, D, H, W, _stream())
+        assert cost.shape[1] == maxdisp
+    out, prob = _ext.load().softmax_softargmin(_f32c(cost), bool(return_prob))
     out = out.unsqueeze(1) if keepdim else out
     return (out, prob) if return_prob else out
 
@@ -359,15 +286,9 @@ def upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners=False):
         cost_lowres = cost_lowres[:, 0]
     assert cost_lowres.dim() == 4
     cs = _f32c(cost_lowres)
-    B, Dl, Hl, Wl = cs.shape
-    ext = _ext.load()
+    _, Dl, Hl, Wl = cs.shape
     with timing.span("upsample_softargmin", Dl, Hl, Wl, int(maxdisp), int(h), int(w)):
-        if ext is not None:
-            return ext.upsample_softargmin(cs, int(maxdisp), int(h), int(w), bool(align_corners))
-        out = torch.empty((B, h, w), device=cs.device, dtype=torch.float32)
-        _lib.call("osa_upsample_softargmin_f32", cs.data_ptr(), out.data_ptr(), B, Dl, Hl, Wl,
-                  int(maxdisp), int(h), int(w), 1 if align_corners else 0, _stream())
-    return out
+        return _ext.load().upsample_softargmin(cs, int(maxdisp), int(h), int(w), bool(align_corners))
 
 
 def context_upsample(disp_low, up_weights, scale_factor=4, softmax_weights=False, gain=1.0):
@@ -377,15 +298,8 @@ def context_upsample(disp_low, up_weights, scale_factor=4, softmax_weights=False
     _chk(disp_low, "disp_low", 4); _chk(up_weights, "up_weights", 4)
     b, c, h, w = disp_low.shape
     assert c == 1 and tuple(up_weights.shape) == (b, 9, h * scale_factor, w * scale_factor)
-    d, wt = _f32c(disp_low), _f32c(up_weights)
-    ext = _ext.load()
     with timing.span("context_upsample", h, w, scale_factor):
-        if ext is not None:
-            out = ext.context_upsample(d, wt, int(scale_factor), bool(softmax_weights), float(gain))
-        else:
-            out = torch.empty((b, h * scale_factor, w * scale_factor), device=d.device, dtype=torch.float32)
-            _lib.call("osa_context_upsample_f32", d.data_ptr(), wt.data_ptr(), out.data_ptr(), b, h, w, int(scale_factor),
-                      1 if softmax_weights else 0, float(gain), _stream())
+        out = _ext.load().context_upsample(_f32c(disp_low), _f32c(up_weights), int(scale_factor), bool(softmax_weights), float(gain))
     od = _sum_dtype(disp_low, up_weights)
     return out if od == torch.float32 else out.to(od)
 
@@ -397,24 +311,17 @@ def preprocess_pair(left_hwc, right_hwc, pad_size, mean=IMAGENET_MEAN, std=IMAGE
     """RightTopPad(SIZE=pad_size, edge) -> TransposeImage -> ToTensor -> NormalizeImage for a stereo pair,
     fused on the GPU (stereo_trans.py:243-267,22-29,48-56).  left/right: [H,W,3] uint8 or float32 CUDA tensors.
     Returns (left, right) [1,3,Hp,Wp]; channels_last=True returns the engine's NHWC4 pair tensor [2,4,1,Hp,Wp]."""
-    import ctypes
     _chk(left_hwc, "left_hwc", 3); _chk(right_hwc, "right_hwc", 3)
     assert left_hwc.shape == right_hwc.shape and left_hwc.shape[2] == 3 and left_hwc.dtype == right_hwc.dtype
     assert left_hwc.dtype in (torch.uint8, torch.float32)
     H, W = left_hwc.shape[:2]
     Hp, Wp = max(pad_size[0], H), max(pad_size[1], W)        # RightTopPad never crops (h = min(h, th))
     l, r = left_hwc.contiguous(), right_hwc.contiguous()
-    m3 = (ctypes.c_float * 3)(*mean); s3 = (ctypes.c_float * 3)(*std)
     if channels_last:
         out = torch.empty((2, 1, Hp, Wp, 4), device=l.device, dtype=torch.float32)
     else:
         out = torch.empty((2, 3, Hp, Wp), device=l.device, dtype=torch.float32)
-    ext = _ext.load()
-    if ext is not None:
-        ext.preprocess_pair(l, r, out, [Hp, Wp], [float(v) for v in mean], [float(v) for v in std], bool(channels_last))
-    else:
-        _lib.call("osa_preprocess_pair_f32", l.data_ptr(), r.data_ptr(), 1 if l.dtype == torch.uint8 else 0, H, W, Hp, Wp,
-                  m3, s3, out.data_ptr(), 1 if channels_last else 0, _stream())
+    _ext.load().preprocess_pair(l, r, out, [Hp, Wp], [float(v) for v in mean], [float(v) for v in std], bool(channels_last))
     if channels_last:
         return out.permute(0, 4, 1, 2, 3)
     return out[0:1], out[1:2]
@@ -487,38 +394,14 @@ def channel_sums(dy: torch.Tensor, x: torch.Tensor | None = None, x_shift: torch
         assert (Px, Cx) == (P, C), "channel_sums: x and dy must agree in shape"
     sh = None if x_shift is None else _f32c(x_shift)
     sc = None if dx_scale is None else _f32c(dx_scale)
-    ext = _ext.load()
-    if ext is not None:
-        out, dx = ext.channel_sums(dy, x, sh, sc, P, C, cs, xcs)
-        return out, (dx if sc is not None else None)
-    lib = _lib.load()
-    need = lib.osa_channel_sums_workspace_bytes(P, C)
-    if not need:
-        raise _lib.EngineError(f"osa_channel_sums: unsupported dims P={P} C={C}")
-    out = torch.empty((2 if x is not None else 1, C), device=dy.device, dtype=torch.float32)
-    ws = torch.empty((need + 3) // 4, device=dy.device, dtype=torch.float32)
-    dx = torch.empty_strided(dy.shape, dy.stride(), device=dy.device, dtype=dy.dtype) if sc is not None else None
-    _lib.call("osa_channel_sums", dy.data_ptr(), int(dy.dtype == torch.float16), cs, _p(x), int(x is not None and x.dtype == torch.float16), xcs,
-              _p(sh), _p(sc), _p(dx), cs, P, C, out.data_ptr(), ws.data_ptr(), need, _stream())
-    return out, dx
+    out, dx = _ext.load().channel_sums(dy, x, sh, sc, P, C, cs, xcs)
+    return out, (dx if sc is not None else None)
 
 
 def channel_sums_list(dys):
     """sum_p dy over a list of equally shaped and strided tensors (osa_channel_sums_multi): [C] fp32, one launch, no concatenation"""
     P, C, cs = cl_rows(dys[0])
-    ext = _ext.load()
-    if ext is not None:
-        return ext.channel_sums_multi(list(dys), P, C, cs)[0]
-    import ctypes
-    lib = _lib.load()
-    need = len(dys) * lib.osa_channel_sums_workspace_bytes(P, C)
-    if not need:
-        raise _lib.EngineError(f"osa_channel_sums_multi: unsupported dims P={P} C={C}")
-    out = torch.empty((1, C), device=dys[0].device, dtype=torch.float32)
-    ws = torch.empty((need + 3) // 4, device=dys[0].device, dtype=torch.float32)
-    _lib.call("osa_channel_sums_multi", (ctypes.c_void_p * len(dys))(*[t.data_ptr() for t in dys]), len(dys), int(dys[0].dtype == torch.float16), cs, P, C,
-              out.data_ptr(), ws.data_ptr(), need, _stream())
-    return out[0]
+    return _ext.load().channel_sums_multi(list(dys), P, C, cs)[0]
 
 
 def channel_affine(u, a, c0, v=None, b=None, relu=False):
@@ -530,10 +413,4 @@ def channel_affine(u, a, c0, v=None, b=None, relu=False):
         assert (Pv, Cv) == (P, C) and b is not None
     a, c0 = _f32c(a), _f32c(c0)
     b = None if b is None else _f32c(b)
-    ext = _ext.load()
-    if ext is not None:
-        return ext.channel_affine(u, v, a, b, c0, P, C, cs, vcs, bool(relu))
-    out = torch.empty_strided(u.shape, u.stride(), device=u.device, dtype=u.dtype)
-    _lib.call("osa_channel_affine", u.data_ptr(), int(u.dtype == torch.float16), cs, _p(v), int(v is not None and v.dtype == torch.float16), vcs,
-              a.data_ptr(), _p(b), c0.data_ptr(), out.data_ptr(), cs, P, C, int(bool(relu)), _stream())
-    return out
+    return _ext.load().channel_affine(u, v, a, b, c0, P, C, cs, vcs, bool(relu))

@@ -3,8 +3,8 @@ extension replacing the reference's helpers must export).
 
 Each op is a `torch.library.custom_op` whose CUDA (= ROCm) implementation calls the C-ABI library, with
   * a fake / meta kernel (shape + dtype inference), so `torch.compile`, `torch.export` and FakeTensor tracing -- e.g. the
-    reference's deploy/export.py -- see an opaque op instead of failing on a ctypes call,
-  * an autograd formula that runs the engine's backward kernels (osa_build_volume_bwd_f32, osa_*softargmin*_bwd_f32),
+    reference's deploy/export.py -- see an opaque op instead of tracing into the engine's launches,
+  * an autograd formula that runs the engine's backward kernels (torch.ops.osa_native.volume_bwd / *softargmin_bwd),
   * autocast behaviour of the eager composition it replaces: fp16 / bf16 in -> same dtype out, arithmetic in fp32.
 There is no CPU kernel: calling an op on CPU tensors raises NotImplementedError from the dispatcher (no fallback).
 
@@ -19,8 +19,8 @@ from __future__ import annotations
 import torch
 from torch.library import custom_op
 
-from . import _lib, ops
-from .ops import _f32c, _stream
+from . import _ext, ops
+from .ops import _f32c
 
 NS = "openstereo_amd"
 
@@ -40,17 +40,8 @@ def _(left, right, maxdisp, num_groups):
 
 
 def _vol_bwd(ctx, dvol, concat, mask_left):
-    l, r = ctx.saved_tensors
-    B, C, H, W = ctx.shape
-    dv = _f32c(dvol)
-    dl = torch.empty((B, C, H, W), device=dv.device, dtype=torch.float32)
-    dr = torch.empty_like(dl)
-    if concat:
-        _lib.call("osa_build_volume_bwd_f32", dv.data_ptr(), None, None, dl.data_ptr(), dr.data_ptr(),
-                  B, C, H, W, ctx.maxdisp, 0, 1, 1 if mask_left else 0, 2 * C, 0, _stream())
-    else:
-        _lib.call("osa_build_volume_bwd_f32", dv.data_ptr(), l.data_ptr(), r.data_ptr(), dl.data_ptr(), dr.data_ptr(),
-                  B, C, H, W, ctx.maxdisp, ctx.groups, 0, 1, ctx.groups, 0, _stream())
+    l, r = (None, None) if concat else ctx.saved_tensors
+    dl, dr = _ext.load().volume_bwd(_f32c(dvol), l, r, list(ctx.shape), ctx.maxdisp, 0 if concat else ctx.groups, concat, mask_left)
     return dl.to(ctx.dtype), dr.to(ctx.dtype)
 
 
@@ -121,9 +112,7 @@ def _sa_setup(ctx, inputs, output):
 
 def _sa_bwd(ctx, g):
     B, D, H, W = ctx.shape
-    gg = _f32c(g.reshape(B, H, W))
-    dp = torch.empty(ctx.shape, device=gg.device, dtype=torch.float32)
-    _lib.call("osa_softargmin_bwd_f32", gg.data_ptr(), dp.data_ptr(), B, D, H, W, _stream())
+    dp = _ext.load().softargmin_bwd(_f32c(g.reshape(B, H, W)), D)
     return dp.to(ctx.dtype), None
 
 
@@ -149,10 +138,8 @@ def _ssa_setup(ctx, inputs, output):
 
 def _ssa_bwd(ctx, g):
     (c,) = ctx.saved_tensors
-    B, D, H, W = c.shape
-    gg = _f32c(g.reshape(B, H, W))
-    dc = torch.empty_like(c)
-    _lib.call("osa_softmax_softargmin_bwd_f32", c.data_ptr(), gg.data_ptr(), dc.data_ptr(), B, D, H, W, _stream())
+    B, _, H, W = c.shape
+    dc = _ext.load().softmax_softargmin_bwd(c, _f32c(g.reshape(B, H, W)))
     return dc.to(ctx.dtype), None
 
 
@@ -181,14 +168,7 @@ def _usa_setup(ctx, inputs, output):
 def _usa_bwd(ctx, g):
     (c,) = ctx.saved_tensors
     maxdisp, h, w, align = ctx.meta
-    B, Dl, Hl, Wl = c.shape
-    gg = _f32c(g)
-    dc = torch.empty_like(c)
-    need = _lib.load().osa_upsample_softargmin_bwd_workspace_bytes(B, Dl, int(h), int(w))
-    ws = torch.empty((need + 3) // 4, device=c.device, dtype=torch.float32)
-    _lib.call("osa_upsample_softargmin_bwd_ws_f32", c.data_ptr(), gg.data_ptr(), dc.data_ptr(), B, Dl, Hl, Wl,
-              int(maxdisp), int(h), int(w), 1 if align else 0, ws.data_ptr(), need, _stream())
-    dc = dc.to(ctx.dtype)
+    dc = _ext.load().upsample_softargmin_bwd(c, _f32c(g), int(maxdisp), int(h), int(w), bool(align)).to(ctx.dtype)
     return (dc.unsqueeze(1) if ctx.five else dc), None, None, None, None
 
 

@@ -1,6 +1,6 @@
 """Timing-only ablations of the fused stride-2 transposed conv (GwcNet hourglass conv6 + redir1 / conv5 + redir2) in the form the
 model runs it: split input, split redir input, split output.  GPU only; needs the experiments build for OSA_DBG
-(tools/build_variant.sh exp -DOSA_EXPERIMENTS; OSA_LIB_PATH=.../exp.so).
+(tools/build_variant.sh exp -DOSA_EXPERIMENTS; OSA_LIB_PATH=openstereo_amd/lib/variants/exp/libopenstereo_amd.so).
 
     python tools/bench_deconv.py [--batch 2] [--dbgs 0,8,32,64,1]
 """

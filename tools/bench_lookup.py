@@ -2,7 +2,7 @@
 (osa_geo_lookup_bwd_f32) at the StereoBase training map (320x736 crop: 80 x 184 at 1/4, C = 8, D = 48, two levels, radius 4): the forms of
 both kernels timed and compared bit for bit.
     bash tools/build_one_variant.sh exp_geo geometry -DOSA_EXPERIMENTS
-    OSA_LIB_PATH=openstereo_amd/lib/variants/exp_geo.so python tools/bench_lookup.py
+    OSA_LIB_PATH=openstereo_amd/lib/variants/exp_geo/libopenstereo_amd.so python tools/bench_lookup.py
 (the form switches exist in the experiments build only: the shipped library always runs the rows forms)"""
 import ctypes
 import os

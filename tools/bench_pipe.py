@@ -2,7 +2,7 @@
 (3x3x3 32->32 @ 48x136x240, split input / split output), with timing-only ablations.  Needs the experiments build:
 
     tools/build_variant.sh exp -DOSA_EXPERIMENTS
-    OSA_LIB_PATH=openstereo_amd/lib/variants/exp.so python tools/bench_pipe.py [--batch 2] [--iters 20]
+    OSA_LIB_PATH=openstereo_amd/lib/variants/exp/libopenstereo_amd.so python tools/bench_pipe.py [--batch 2] [--iters 20]
 
 Every variant runs interleaved in ONE process (rounds x variants), medians are reported (cdna_hip_programming.md 5.4 rule 24)."""
 import argparse
@@ -19,7 +19,6 @@ from openstereo_amd.engine import PackedConv3d  # noqa: E402
 
 VARIANTS = [  # name, env
     ("classic", {}),
-    ("classic no-ranges", {"BENCH_NO_RANGES": "1"}),
     ("pipe", {"OSA_PIPE": "1"}),
     ("pipe 1wg/cu", {"OSA_PIPE": "1", "OSA_PIPE_WGS": "1"}),
     ("pipe no-dma", {"OSA_PIPE": "1", "OSA_DBG": "1"}),
@@ -30,18 +29,7 @@ VARIANTS = [  # name, env
     ("classic no-staging", {"OSA_DBG": "1"}),
     ("classic no-epilogue", {"OSA_DBG": "8"}),
 ]
-KEYS = ("OSA_PIPE", "OSA_PIPE_WGS", "OSA_DBG", "BENCH_NO_RANGES")
-
-
-def no_ranges(layer, xs):
-    """The same launch with a NULL osa_f16x3_ranges block: no operand scales, no max |y| tracking (cost of the range machinery)."""
-    from openstereo_amd import _lib
-    orig = _lib.F16x3Ranges
-    _lib.F16x3Ranges = lambda *a: None
-    try:
-        return layer(xs, out_split=True)
-    finally:
-        _lib.F16x3Ranges = orig
+KEYS = ("OSA_PIPE", "OSA_PIPE_WGS", "OSA_DBG")
 
 
 def main():
@@ -69,7 +57,7 @@ def main():
             for k in KEYS:
                 os.environ.pop(k, None)
             os.environ.update(env)
-            run = (lambda: layer(xs, out_split=True)) if "BENCH_NO_RANGES" not in env else (lambda: no_ranges(layer, xs))
+            run = lambda: layer(xs, out_split=True)
             run()
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

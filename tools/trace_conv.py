@@ -1,6 +1,6 @@
 """In-kernel timeline of the fused transposed conv (or any conv launch): experiments build + OSA_DBG=256.
 
-    OSA_LIB_PATH=.../exp.so python tools/trace_conv.py [--batch 2] [--layer conv6|conv5|c32]
+    OSA_LIB_PATH=openstereo_amd/lib/variants/exp/libopenstereo_amd.so python tools/trace_conv.py [--batch 2] [--layer conv6|conv5|c32]
 
 Prints, per traced workgroup (every 97th) and wave, the microseconds between the phase stamps of conv_kernel.h:
 0 kernel entry | per staging pass: pass start, own loads landed, brick complete (barrier), taps done | 20 epilogue start (barrier) | 21+i tile i done."""
