@@ -9,10 +9,11 @@
 Nothing in the reference tree is edited; only module / class attributes are rebound.  Works with whatever
 subset of reference modules is importable (models that need timm etc. are skipped).
 
-Functions: every replacement is DIFFERENTIABLE -- when autograd is recording and an argument requires grad the
-call goes through `openstereo_amd.autograd` (forward and backward on the engine's kernels), otherwise through the
-non-recording `openstereo_amd.ops` entry.  A reference trainer running under the patch therefore trains exactly
-as before (cost_volume.py:68-92 and disp_regression.py:8-12 are differentiable compositions).
+Functions: every replacement is DIFFERENTIABLE.  The volume constructors and regression heads are the `openstereo_amd.ops`
+entries, whose `osa_native` ops carry their own autograd kernels (forward and backward on the engine's kernels, recording or
+not: there is one call, not a recording and a non-recording one); a branch on "gradients are needed" remains only where the
+two modes run different kernels or return different dtypes, and says so.  A reference trainer running under the patch
+therefore trains exactly as before (cost_volume.py:68-92 and disp_regression.py:8-12 are differentiable compositions).
 
 Classes: the engine mirrors in `openstereo_amd.models` use the reference's attribute names, so their methods can
 be grafted onto the reference classes without rebuilding a model: parameters stay where they are (same
@@ -42,23 +43,19 @@ def _needs_grad(*tensors) -> bool:
 # ----------------------------------------------------------------------------- differentiable drop-in functions
 def build_gwc_volume(refimg_fea, targetimg_fea, maxdisp, num_groups):
     """cost_volume.py:68-78"""
-    if _needs_grad(refimg_fea, targetimg_fea):
-        from . import autograd as AG
-        return AG.build_gwc_volume(refimg_fea, targetimg_fea, maxdisp, num_groups).to(refimg_fea.dtype)
     return ops.build_gwc_volume(refimg_fea, targetimg_fea, maxdisp, num_groups)
 
 
 def build_concat_volume(refimg_fea, targetimg_fea, maxdisp, mask_left=True):
     """cost_volume.py:81-92 (mask_left=False: igev/submodule.py:216-227)"""
-    if _needs_grad(refimg_fea, targetimg_fea):
-        from . import autograd as AG
-        return AG.build_concat_volume(refimg_fea, targetimg_fea, maxdisp, mask_left).to(refimg_fea.dtype)
     return ops.build_concat_volume(refimg_fea, targetimg_fea, maxdisp, mask_left=mask_left)
 
 
 def correlation_volume(left_feature, right_feature, max_disp):
     """cost_volume.py:32-41"""
     if _needs_grad(left_feature, right_feature):
+        # not a twin of the line below: training runs the group-wise kernel with one group (autograd.correlation_volume), whose forward bits
+        # may differ from the dedicated correlation kernel's
         from . import autograd as AG
         return AG.correlation_volume(left_feature, right_feature, max_disp).to(left_feature.dtype)
     return ops.correlation_volume(left_feature, right_feature, max_disp)
@@ -66,7 +63,7 @@ def correlation_volume(left_feature, right_feature, max_disp):
 
 def build_corr_volume(img_left, img_right, max_disp):
     """cost_volume.py:95-105 (planes d >= W repeat plane 0, see ops.build_corr_volume)"""
-    if _needs_grad(img_left, img_right):
+    if _needs_grad(img_left, img_right):                 # (ops.build_corr_volume fills the repeated planes in place)
         vol = correlation_volume(img_left, img_right, max_disp)
         W = img_left.shape[-1]
         return vol if max_disp <= W else torch.cat((vol[:, :W], vol[:, :1].expand(-1, max_disp - W, -1, -1)), 1)
@@ -75,24 +72,20 @@ def build_corr_volume(img_left, img_right, max_disp):
 
 def cat_fms(reference_fm, target_fm, max_disp=192, start_disp=0, dilation=1):
     """psmnet_cost_processor.py:9-50 (always fp32, like the reference's buffer)"""
-    if _needs_grad(reference_fm, target_fm):
-        if start_disp != 0 or dilation != 1:             # no backward kernel for the general sampling: the reference's own (differentiable) code
-            for mod, attr, old in _saved:
-                if attr == "cat_fms" and callable(old):
-                    return old(reference_fm, target_fm, max_disp, start_disp, dilation)
-            raise NotImplementedError("cat_fms with start_disp / dilation has no autograd path on the engine")
-        from . import autograd as AG
-        return AG.build_concat_volume(reference_fm.float(), target_fm.float(), max_disp)
+    if _needs_grad(reference_fm, target_fm) and (start_disp != 0 or dilation != 1):
+        for mod, attr, old in _saved:                    # no backward kernel for the general sampling: the reference's own (differentiable) code
+            if attr == "cat_fms" and callable(old):
+                return old(reference_fm, target_fm, max_disp, start_disp, dilation)
+        raise NotImplementedError("cat_fms with start_disp / dilation has no autograd path on the engine")
     return ops.cat_fms(reference_fm, target_fm, max_disp, start_disp, dilation)
 
 
 def disparity_regression(x, maxdisp, keepdim=True):
     """disp_regression.py:8-12 (keepdim=True) / gwcnet_disp_processor.py:22-26 (keepdim=False)"""
-    if _needs_grad(x):
-        from . import autograd as AG
-        assert len(x.shape) == 4
-        return AG.disparity_regression(x, maxdisp, keepdim).to(x.dtype)
-    return ops.disparity_regression(x, maxdisp, keepdim)
+    out = ops.disparity_regression(x, maxdisp, keepdim)
+    # one computation; the branch only selects the result dtype, which differs inside an autocast region: the entry returns fp32 there
+    # (`sum` is on autocast's fp32 list), a reference trainer's loss code gets x's dtype
+    return out.to(x.dtype) if _needs_grad(x) else out
 
 
 def context_upsample(disp_low, up_weights, scale_factor=4):

@@ -1,11 +1,15 @@
 """Differentiable wrappers (training path, SURVEY 8b "Autograd / AMP", Appendix C).
 
-Every Function's forward AND backward run on the engine's HIP kernels:
+Forward AND backward of everything here run on the engine's HIP kernels:
   * volume constructors  -> osa_build_volume_f32 / osa_build_volume_bwd_f32
   * regression heads     -> osa_*softargmin*_f32 / *_bwd_f32
-  * Conv3d / ConvTranspose3d / Conv2d -> the MFMA implicit-GEMM kernel (forward), the SAME kernel with
-    role-swapped / flipped weight packing for the data gradient, and the fp32-MFMA wgrad kernel for the
-    weight gradient.
+    These six entries hold no gradient code: they are compositions over the `osa_native` ops, which are
+    differentiable in C++ (csrc/torch_ext.cpp registers their Autograd kernels) -- one definition, shared
+    with `openstereo_amd.ops` and `openstereo_amd.attach`.
+  * Conv3d / ConvTranspose3d / Conv2d -> torch.autograd.Functions: the MFMA implicit-GEMM kernel (forward),
+    the SAME kernel with role-swapped / flipped weight packing for the data gradient, and the fp32-MFMA wgrad
+    kernel for the weight gradient.  The batched weight-gradient launch of the deferring Functions is one
+    helper (`_wgrad_items`).
 BatchNorm (batch statistics, SyncBN), activations and residual adds stay ordinary torch modules in
 training mode, so their semantics (running-stat updates, DDP/SyncBN hooks) are exactly the reference's;
 fusion of BN/activation into the conv epilogue is an inference-only optimisation.
@@ -25,123 +29,47 @@ from .ops import _f32c, channel_sums, cl_rows, empty_cl, is_cl, to_cl
 from .ranges import input_meta, attach_meta
 
 
-# Every Function runs its forward with autocast switched off and floating inputs cast to fp32 (torch.amp.custom_fwd): the kernels compute
-# in fp32-class arithmetic whatever the surrounding region says; the callers below cast the result to the dtype the reference's op would
+# The convolution Functions run their forward with autocast switched off and floating inputs cast to fp32 (torch.amp.custom_fwd): the kernels
+# compute in fp32-class arithmetic whatever the surrounding region says; their callers cast the result to the dtype the reference's op would
 # have produced there (openstereo_amd/amp.py).  Backward runs under the same (disabled) autocast state (custom_bwd).
 _fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _bwd = torch.amp.custom_bwd(device_type="cuda")
 
 
-# ----------------------------------------------------------------------------- volumes
-class _GwcVolume(torch.autograd.Function):
-    @staticmethod
-    @_fwd
-    def forward(ctx, left, right, maxdisp, num_groups):
-        l, r = _f32c(left), _f32c(right)
-        ctx.save_for_backward(l, r)
-        ctx.meta = (maxdisp, num_groups, left.dtype)
-        return ops._build(l, r, num_groups, None, None, maxdisp, ops.NCDHW)
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, dvol):
-        l, r = ctx.saved_tensors
-        maxdisp, G, dt = ctx.meta
-        B, C, H, W = l.shape
-        dl, dr = _ext.load().volume_bwd(_f32c(dvol), l, r, [B, C, H, W], maxdisp, G, False, True)
-        return dl.to(dt), dr.to(dt), None, None
-
-
-class _ConcatVolume(torch.autograd.Function):
-    @staticmethod
-    @_fwd
-    def forward(ctx, left, right, maxdisp, mask_left):
-        l, r = _f32c(left), _f32c(right)
-        ctx.meta = (maxdisp, mask_left, left.dtype, tuple(l.shape))
-        return ops._build(None, None, 0, l, r, maxdisp, ops.NCDHW, mask_left=mask_left)
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, dvol):
-        maxdisp, mask_left, dt, (B, C, H, W) = ctx.meta
-        dl, dr = _ext.load().volume_bwd(_f32c(dvol), None, None, [B, C, H, W], maxdisp, 0, True, bool(mask_left))
-        return dl.to(dt), dr.to(dt), None, None
-
-
+# ----------------------------------------------------------------------------- volumes and regression heads
+# No Function here: the `osa_native` ops these entries launch are differentiable in C++ (csrc/torch_ext.cpp, TORCH_LIBRARY_IMPL(osa_native,
+# Autograd): backward = the engine's *_bwd kernels), and the `ops` entries around them are differentiable compositions -- a cast to
+# contiguous fp32 (the ops take nothing else and have no autocast kernels; the cast's own backward returns the gradient in the leaf's
+# dtype), the op, the result dtype.  What is left to say here is the result dtype of the training path: fp32 whatever the features are.
+# The models reach these through the module attribute (`AG.<name>(...)`) at call time, so a caller can rebind them.
 def build_gwc_volume(refimg_fea, targetimg_fea, maxdisp, num_groups):
-    assert refimg_fea.shape[1] % num_groups == 0
-    return _GwcVolume.apply(refimg_fea, targetimg_fea, maxdisp, num_groups)
+    """-> fp32 [B, num_groups, maxdisp, H, W]"""
+    return ops.build_gwc_volume(refimg_fea.float(), targetimg_fea.float(), maxdisp, num_groups)
 
 
 def build_concat_volume(refimg_fea, targetimg_fea, maxdisp, mask_left=True):
-    return _ConcatVolume.apply(refimg_fea, targetimg_fea, maxdisp, mask_left)
+    """-> fp32 [B, 2C, maxdisp, H, W]"""
+    return ops.build_concat_volume(refimg_fea.float(), targetimg_fea.float(), maxdisp, mask_left)
 
 
 def correlation_volume(left_feature, right_feature, max_disp):
-    return _GwcVolume.apply(left_feature, right_feature, max_disp, 1)[:, 0]
-
-
-# ----------------------------------------------------------------------------- regression
-class _SoftArgmin(torch.autograd.Function):
-    @staticmethod
-    @_fwd
-    def forward(ctx, prob):
-        ctx.shape = tuple(prob.shape)
-        return ops.disparity_regression(prob, prob.shape[1], keepdim=False)
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, dout):
-        return _ext.load().softargmin_bwd(_f32c(dout), ctx.shape[1])
-
-
-class _SoftmaxSoftArgmin(torch.autograd.Function):
-    @staticmethod
-    @_fwd
-    def forward(ctx, cost):
-        c = _f32c(cost)
-        ctx.save_for_backward(c)
-        return ops.softmax_disparity_regression(c, keepdim=False)
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, dout):
-        (c,) = ctx.saved_tensors
-        return _ext.load().softmax_softargmin_bwd(c, _f32c(dout))
-
-
-class _UpsampleSoftArgmin(torch.autograd.Function):
-    @staticmethod
-    @_fwd
-    def forward(ctx, cost_low, maxdisp, h, w, align_corners):
-        c = _f32c(cost_low)
-        ctx.save_for_backward(c)
-        ctx.meta = (maxdisp, h, w, align_corners)
-        return ops.upsample_softargmin(c, maxdisp, h, w, align_corners)
-
-    @staticmethod
-    @_bwd
-    def backward(ctx, dout):
-        (c,) = ctx.saved_tensors
-        maxdisp, h, w, align = ctx.meta
-        return _ext.load().upsample_softargmin_bwd(c, _f32c(dout), int(maxdisp), int(h), int(w), bool(align)), None, None, None, None
+    """-> fp32 [B, max_disp, H, W]: the group-wise volume with ONE group (not ops.correlation_volume: another kernel, other forward bits)"""
+    return ops.build_gwc_volume(left_feature.float(), right_feature.float(), max_disp, 1)[:, 0]
 
 
 def disparity_regression(prob, maxdisp, keepdim=True):
-    assert len(prob.shape) == 4 and prob.shape[1] == maxdisp
-    out = _SoftArgmin.apply(prob)
-    return out.unsqueeze(1) if keepdim else out
+    """-> prob's dtype; fp32 inside an autocast region"""
+    return ops.disparity_regression(prob, maxdisp, keepdim)
 
 
 def softmax_disparity_regression(cost, keepdim=True):
-    out = _SoftmaxSoftArgmin.apply(cost)
-    return out.unsqueeze(1) if keepdim else out
+    """-> fp32"""
+    return ops.softmax_disparity_regression(cost, keepdim=keepdim)
 
 
 def upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners=False):
-    if cost_lowres.dim() == 5:
-        cost_lowres = cost_lowres[:, 0]
-    return _UpsampleSoftArgmin.apply(cost_lowres, maxdisp, h, w, align_corners)
+    """-> fp32 [B, h, w]"""
+    return ops.upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners)
 
 
 # ----------------------------------------------------------------------------- convolutions
@@ -480,22 +408,75 @@ def _cat_batch(ts, C=None):
         return ts[0]
     return torch.cat([t.permute(0, 2, 3, 4, 1) if C is None else t.permute(0, 2, 3, 4, 1)[..., :C] for t in ts], 0).permute(0, 4, 1, 2, 3)
 
+
+def _wgrad_items(items, wf, Ci, Co, k, stride, pad, dil, transposed, precision, need_w=True, need_b=False, xcs=None, dycs=None, chans=None):
+    """(dw, db) of one weight over every queued item of one deferral key -- the `run` the conv Functions hand to _defer_wgrad: ONE
+    weight-gradient launch and one bias-gradient sum.  items: (x, dy) NDHWC pairs, from the fp32 Functions with their f16x3 range blocks
+    behind (x, dy, xmeta, dymeta); wf: the weight as the kernel sees it (shape of dw).  One item: the plain call; equally laid out items,
+    at most 24: the list form (no copy); anything else: the batch concatenation.  xcs / dycs: channel strides of fp16 tensors whose rows
+    are wider than their logical channels; chans = (x, dy) logical channel counts, which is all the concatenation of such tensors keeps."""
+    xl, dl = [it[0] for it in items], [it[1] for it in items]
+    g = None
+    if need_w:
+        B, _, D, H, W = xl[0].shape
+        Do, Ho, Wo = dl[0].shape[2:]
+        xm = dm = None
+        if precision == "f16x3" and len(items[0]) == 4:
+            from .ranges import combine_meta
+            xm = combine_meta(*[it[2] if it[2] is not None else input_meta(it[0]) for it in items])
+            dm = combine_meta(*[it[3] for it in items])
+        g = torch.empty_like(wf)
+        geom = (Ci, Do, Ho, Wo, Co, k, stride, pad, dil, transposed, precision, xm, dm)
+        if len(items) == 1:
+            _wgrad(xl[0], dl[0], g, B, D, H, W, *geom, xcs=xcs, dycs=dycs)
+        elif MULTI_WGRAD and len(items) <= 24 and _same_layout(xl) and _same_layout(dl):
+            _wgrad(xl, dl, g, len(items) * B, D, H, W, *geom, xcs=xcs, dycs=dycs)
+        else:
+            cx, cdy = chans or (None, None)
+            xs, dys = _cat_batch(xl, cx), _cat_batch(dl, cdy)
+            _wgrad(xs, dys, g, xs.shape[0], D, H, W, *geom)
+            if chans is None:
+                dl = [dys]                                  # (fp32 form: the bias sum reads the one concatenated tensor, not the items)
+    return g, (_bias_grad_items(dl, Co) if need_b else None)
+
+
+def _conv_weights(ctx, x, w, w2, bias, cache, flat):
+    """Shared forward prologue of _Conv3d / _Conv3dF16IO -> (x, w, w2 as 3-D operands, the fp32 weight the launch packs, the fp32 bias).
+    flat: the 2-D case -- x is [B,Ci,H,W], w [Co,Ci,kh,kw] (the D = 1 case of the same kernels), the result [B,Co,H,W].
+    w2: a second layer over the same input, stacked on the output axis -- ONE forward / data-gradient / weight-gradient launch for both
+    (ConvGRU's convz | convr read the same [h | x], update.py:38-39).  The concatenation is memoised with the packs.
+    bias: added in the conv launch's epilogue (r5: one elementwise launch less per biased layer and call -- ~200 per StereoBase step)."""
+    ctx.flat = flat
+    if flat:
+        x, w = x.unsqueeze(2), w.unsqueeze(2)
+        w2 = None if w2 is None else w2.unsqueeze(2)
+    ctx.co1 = None if w2 is None else w.shape[0]
+    wf = _f32c(w) if w2 is None else _memo(cache, "wcat", lambda: torch.cat([_f32c(w.detach()), _f32c(w2.detach())], 0))
+    ctx.bias_dt = None if bias is None else bias.dtype
+    ctx.cache = cache
+    return x, w, w2, wf, (None if bias is None else _f32c(bias.detach()))
+
+
+def _conv_grads(ctx, dx, dw, db, nargs, iw2, ib):
+    """Shared backward epilogue of _Conv3d / _Conv3dF16IO: the result tuple over forward's `nargs` arguments -- dw back to 2-D (flat) and
+    split over the stacked pair (w at 1, w2 at iw2), db in the bias's dtype at ib."""
+    if dw is not None and ctx.flat:
+        dw = dw[:, :, 0]
+    out = [None] * nargs
+    out[0], out[1], out[ib] = dx, dw, (None if db is None else db.to(ctx.bias_dt))
+    if ctx.co1 is not None and dw is not None:
+        out[1], out[iw2] = dw[:ctx.co1], dw[ctx.co1:]
+    return tuple(out)
+
+
 class _Conv3d(torch.autograd.Function):
     """y = conv3d(x, w) (no bias).  x: logical [B,Ci,D,H,W] (any strides); y: NDHWC-strided [B,Co,...]."""
 
     @staticmethod
     @_fwd
     def forward(ctx, x, w, stride, pad, dil, precision, cache=None, w2=None, bias=None, flat=False):
-        # flat: the 2-D case -- x is [B,Ci,H,W], w [Co,Ci,kh,kw] (the D = 1 case of the same kernels), the result [B,Co,H,W]
-        ctx.flat = flat
-        if flat:
-            x, w = x.unsqueeze(2), w.unsqueeze(2)
-            w2 = None if w2 is None else w2.unsqueeze(2)
+        x, w, w2, wf, bf = _conv_weights(ctx, x, w, w2, bias, cache, flat)
         xc = to_cl(x)                               # NDHWC, channels padded to a multiple of 4 with zeros
-        # w2: a second layer over the same input, stacked on the output axis -- ONE forward / data-gradient / weight-gradient launch for
-        # both (ConvGRU's convz | convr read the same [h | x], update.py:38-39).  The concatenation is memoised with the packs.
-        ctx.co1 = None if w2 is None else w.shape[0]
-        wf = _f32c(w) if w2 is None else _memo(cache, "wcat", lambda: torch.cat([_f32c(w.detach()), _f32c(w2.detach())], 0))
         Co, Ci = wf.shape[:2]
         k = tuple(wf.shape[2:])
         packed, osc = _pack(wf, Ci, Co, k, "fwd", precision, cache)
@@ -504,13 +485,10 @@ class _Conv3d(torch.autograd.Function):
         oshape = (_out(D, k[0], pad[0], dil[0], sd), _out(H, k[1], pad[1], dil[1], stride), _out(W, k[2], pad[2], dil[2], stride))
         # one max |x| reduction serves the forward conv and (ctx.xmeta) the f16x3 weight gradient; kept on ctx, not on the tensor object
         xmeta = input_meta(xc) if precision == "f16x3" else None
-        # bias: added in the conv launch's epilogue (r5: one elementwise launch less per biased layer and call -- ~200 per StereoBase step)
-        ctx.bias_dt = None if bias is None else bias.dtype
-        y = _run_conv(xc, packed, osc, Ci, Co, k, stride, pad, dil, precision, oshape, xmeta, None if bias is None else _f32c(bias.detach()))
+        y = _run_conv(xc, packed, osc, Ci, Co, k, stride, pad, dil, precision, oshape, xmeta, bf)
         ctx.save_for_backward(xc, wf)
         ctx.xmeta = xmeta
         ctx.meta = (stride, pad, dil, precision, tuple(x.shape), x.dtype)
-        ctx.cache = cache
         _defer_note_use(cache, ctx.needs_input_grad[1] or (w2 is not None and ctx.needs_input_grad[7]) or (bias is not None and ctx.needs_input_grad[8]),
                         w, w2, flat, ctx.co1, bias)
         # The result is a channel slice (and, flat, a squeeze) of the internal NDHWC allocation.  Returned as a view, autograd refuses
@@ -547,34 +525,10 @@ class _Conv3d(torch.autograd.Function):
         need_b = ctx.bias_dt is not None and ctx.needs_input_grad[8]
         db = None
         if need_w or need_b:
-            Do, Ho, Wo = dyc.shape[2:]
-
-            def run(items):                                        # one weight-gradient launch (and one bias-gradient sum) over every queued (x, dy) pair of this weight
-                from .ranges import combine_meta
-                xl, dl = [it[0] for it in items], [it[1] for it in items]
-                as_list = MULTI_WGRAD and 1 < len(items) <= 24 and _same_layout(xl) and _same_layout(dl)
-                g = None
-                if need_w:
-                    xm = dm = None
-                    if precision == "f16x3":
-                        xm = combine_meta(*[it[2] if it[2] is not None else input_meta(it[0]) for it in items])
-                        dm = combine_meta(*[it[3] for it in items])
-                    g = torch.empty_like(wf)
-                    if as_list:
-                        _wgrad(xl, dl, g, len(items) * B, D, H, W, Ci, Do, Ho, Wo, Co, k, stride, pad, dil, 0, precision, xm, dm)
-                    else:
-                        xs, dl = _cat_batch(xl), [_cat_batch(dl)]
-                        _wgrad(xs, dl[0], g, xs.shape[0], D, H, W, Ci, Do, Ho, Wo, Co, k, stride, pad, dil, 0, precision, xm, dm)
-                return g, (_bias_grad_items(dl, Co) if need_b else None)
+            run = lambda items: _wgrad_items(items, wf, Ci, Co, k, stride, pad, dil, 0, precision, need_w, need_b)
             dw, db = _defer_wgrad(ctx.cache, ("f32io", precision, tuple(xc.shape[1:]), tuple(dyc.shape[1:]), stride, pad, dil, need_w, need_b),
                                   (xc, dyc, ctx.xmeta, dymeta), run)
-            if db is not None:
-                db = db.to(ctx.bias_dt)
-        if dw is not None and ctx.flat:
-            dw = dw[:, :, 0]
-        if ctx.co1 is not None:
-            return dx, (None if dw is None else dw[:ctx.co1]), None, None, None, None, None, (None if dw is None else dw[ctx.co1:]), db, None
-        return dx, dw, None, None, None, None, None, None, db, None
+        return _conv_grads(ctx, dx, dw, db, 10, 7, 8)
 
 
 NATIVE_F16_IO = os.environ.get("OSA_NATIVE_F16_IO", "1") != "0"
@@ -611,13 +565,8 @@ class _Conv3dF16IO(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, pad, dil, cache, w2, bias, flat, out_dtype):
         with torch.autocast("cuda", enabled=False):
-            ctx.flat = flat
-            if flat:
-                x, w = x.unsqueeze(2), w.unsqueeze(2)
-                w2 = None if w2 is None else w2.unsqueeze(2)
+            x, w, w2, wf, bf = _conv_weights(ctx, x, w, w2, bias, cache, flat)
             xc, xcs = _as_cl16(x)
-            ctx.co1 = None if w2 is None else w.shape[0]
-            wf = _f32c(w) if w2 is None else _memo(cache, "wcat", lambda: torch.cat([_f32c(w.detach()), _f32c(w2.detach())], 0))
             Co, Ci = wf.shape[:2]
             k = tuple(wf.shape[2:])
             packed, _ = _pack(wf, Ci, Co, k, "fwd", "f16", cache)
@@ -628,12 +577,9 @@ class _Conv3dF16IO(torch.autograd.Function):
             y = empty_cl(B, CoS, *oshape, xc.device, torch.float16 if o16 else torch.float32)
             if CoS != Co:
                 y.zero_()
-            bf = None if bias is None else _f32c(bias.detach())
-            ctx.bias_dt = None if bias is None else bias.dtype
             _launch_f16(xc, xcs, packed, y, CoS, [B, D, H, W, Ci], Co, k, pad, dil, IN_F16 | (OUT_F16 if o16 else 0), bf)
             ctx.save_for_backward(xc, wf)
             ctx.meta = (pad, dil, xcs, x.dtype)
-            ctx.cache = cache
             _defer_note_use(cache, ctx.needs_input_grad[1] or (w2 is not None and ctx.needs_input_grad[5]) or (bias is not None and ctx.needs_input_grad[6]),
                             w, w2, flat, ctx.co1, bias)
             return _alias(y[:, :Co, 0] if flat else y[:, :Co])
@@ -666,30 +612,9 @@ class _Conv3dF16IO(torch.autograd.Function):
             need_b = ctx.bias_dt is not None and ctx.needs_input_grad[6]
             db = None
             if need_w or need_b:
-                Do, Ho, Wo = dyc.shape[2:]
-
-                def run(items):                                    # one weight-gradient launch (and one bias-gradient sum) over every queued (x, dy) pair of this weight
-                    xl, dl = [it[0] for it in items], [it[1] for it in items]
-                    as_list = MULTI_WGRAD and 1 < len(items) <= 24 and _same_layout(xl) and _same_layout(dl)
-                    g = None
-                    if need_w:
-                        g = torch.empty_like(wf)
-                        if len(items) == 1:
-                            _wgrad(xl[0], dl[0], g, B, D, H, W, Ci, Do, Ho, Wo, Co, k, 1, pad, dil, 0, "f16", xcs=xcs, dycs=dycs)
-                        elif as_list:
-                            _wgrad(xl, dl, g, len(items) * B, D, H, W, Ci, Do, Ho, Wo, Co, k, 1, pad, dil, 0, "f16", xcs=xcs, dycs=dycs)
-                        else:                                      # (rows wider than the logical channels are dropped by the concatenation)
-                            xs, dys = _cat_batch(xl, Ci), _cat_batch(dl, Co if fin else None)
-                            _wgrad(xs, dys, g, xs.shape[0], D, H, W, Ci, Do, Ho, Wo, Co, k, 1, pad, dil, 0, "f16", xcs=xs.shape[1], dycs=dys.shape[1])
-                    return g, (_bias_grad_items(dl, Co) if need_b else None)
+                run = lambda items: _wgrad_items(items, wf, Ci, Co, k, 1, pad, dil, 0, "f16", need_w, need_b, xcs, dycs, (Ci, Co if fin else None))
                 dw, db = _defer_wgrad(ctx.cache, ("f16io", tuple(xc.shape[1:]), tuple(dyc.shape[1:]), xcs, dycs, pad, dil, fin, need_w, need_b), (xc, dyc), run)
-                if dw is not None and ctx.flat:
-                    dw = dw[:, :, 0]
-                if db is not None:
-                    db = db.to(ctx.bias_dt)
-            if ctx.co1 is not None:
-                return dx, (None if dw is None else dw[:ctx.co1]), None, None, None, (None if dw is None else dw[ctx.co1:]), db, None, None
-            return dx, dw, None, None, None, None, db, None, None
+            return _conv_grads(ctx, dx, dw, db, 9, 5, 6)
 
 
 def _launch_f16(x, xcs, packed, y, ycs, xdims, Co, k, pad, dil, act, bias):
@@ -789,17 +714,7 @@ class _ConvTranspose2d(torch.autograd.Function):
             dxc = _run_conv(dyc, packed, osc, Co, Ci, (1, k, k), 2, (0, pad, pad), (1, 1, 1), precision, (1, H, W))
             dx = dxc[:, :Ci, 0].to(xdt)
         if ctx.needs_input_grad[1]:
-            Ho, Wo = dyc.shape[3:]
-
-            def run(items):                                        # one weight-gradient launch over every queued (x, dy) pair of this weight
-                xl, dl = [it[0] for it in items], [it[1] for it in items]
-                g = torch.empty_like(w5)
-                if MULTI_WGRAD and 1 < len(items) <= 24 and _same_layout(xl) and _same_layout(dl):
-                    _wgrad(xl, dl, g, len(items) * B, 1, H, W, Ci, 1, Ho, Wo, Co, (1, k, k), 2, (0, pad, pad), (1, 1, 1), 1, precision)
-                else:
-                    xs, dys = _cat_batch(xl), _cat_batch(dl)
-                    _wgrad(xs, dys, g, xs.shape[0], 1, H, W, Ci, 1, Ho, Wo, Co, (1, k, k), 2, (0, pad, pad), (1, 1, 1), 1, precision)
-                return g, None
+            run = lambda items: _wgrad_items(items, w5, Ci, Co, (1, k, k), 2, (0, pad, pad), (1, 1, 1), 1, precision)
             dw, _ = _defer_wgrad(ctx.cache, ("deconv2d", precision, tuple(xc.shape[1:]), tuple(dyc.shape[1:]), k, pad), (xc, dyc), run)
             if dw is not None:
                 dw = dw[:, :, 0]

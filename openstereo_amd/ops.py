@@ -106,39 +106,41 @@ def to_ncdhw(x: torch.Tensor, channels: int | None = None) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------- volumes
-def _build(lg, rg, G, lc, rc, maxdisp, layout, mask_left=True, out=None, vol_channels=None, c_off=0):
+def _build(lg, rg, G, lc, rc, maxdisp, mask_left=True, vol_channels=None):
+    """the in-place launch into a fresh NDHWC buffer (not differentiable: the inference path of the engine models)"""
     ref = lg if lg is not None else lc
     B, _, H, W = ref.shape
     Cg = lg.shape[1] if lg is not None else 0
     Cc = lc.shape[1] if lc is not None else 0
     nch = (G if Cg else 0) + 2 * Cc
     VC = nch if vol_channels is None else vol_channels
-    if out is None:
-        if layout == NDHWC:
-            out = empty_cl(B, VC, maxdisp, H, W, ref.device)
-            if VC > c_off + nch or c_off > 0:
-                out.zero_()
-        else:
-            out = torch.empty((B, VC, maxdisp, H, W), device=ref.device, dtype=torch.float32)
-    meta = attach_meta(out) if layout == NDHWC else None     # range block for f16x3 consumers
-    with timing.span("build_volume", Cg, G, Cc, layout, maxdisp, H, W):
-        _ext.load().build_volume(lg, rg, G, lc, rc, out, layout, VC, c_off, maxdisp, bool(mask_left), meta)
+    out = empty_cl(B, VC, maxdisp, H, W, ref.device)
+    if VC > nch:
+        out.zero_()
+    meta = attach_meta(out)                                  # range block for f16x3 consumers
+    with timing.span("build_volume", Cg, G, Cc, NDHWC, maxdisp, H, W):
+        _ext.load().build_volume(lg, rg, G, lc, rc, out, NDHWC, VC, 0, maxdisp, bool(mask_left), meta)
     return out
 
 
+# The NCDHW volumes go through the allocating `osa_native.gwc_volume` / `concat_volume` ops: differentiable in C++ (csrc/torch_ext.cpp), so
+# a volume of features that require grad carries a grad_fn, here as everywhere.
 def build_gwc_volume(refimg_fea, targetimg_fea, maxdisp, num_groups):
     """cost_volume.py:68-78 -> [B, num_groups, maxdisp, H, W], contiguous, input dtype."""
     _chk(refimg_fea, "refimg_fea", 4); _chk(targetimg_fea, "targetimg_fea", 4)
     B, Cn, H, W = refimg_fea.shape
     assert Cn % num_groups == 0                                   # cost_volume.py:61
-    v = _build(_f32c(refimg_fea), _f32c(targetimg_fea), num_groups, None, None, maxdisp, NCDHW)
+    with timing.span("build_volume", Cn, num_groups, 0, NCDHW, maxdisp, H, W):
+        v = _ext.load().gwc_volume(_f32c(refimg_fea), _f32c(targetimg_fea), int(maxdisp), int(num_groups))
     return v if refimg_fea.dtype == torch.float32 else v.to(refimg_fea.dtype)
 
 
 def build_concat_volume(refimg_fea, targetimg_fea, maxdisp, mask_left=True):
     """cost_volume.py:81-92 -> [B, 2C, maxdisp, H, W]. mask_left=False is IGEV's copy (submodule.py:216-227)."""
     _chk(refimg_fea, "refimg_fea", 4); _chk(targetimg_fea, "targetimg_fea", 4)
-    v = _build(None, None, 0, _f32c(refimg_fea), _f32c(targetimg_fea), maxdisp, NCDHW, mask_left=mask_left)
+    B, Cn, H, W = refimg_fea.shape
+    with timing.span("build_volume", 0, 0, Cn, NCDHW, maxdisp, H, W):
+        v = _ext.load().concat_volume(_f32c(refimg_fea), _f32c(targetimg_fea), int(maxdisp), bool(mask_left))
     return v if refimg_fea.dtype == torch.float32 else v.to(refimg_fea.dtype)
 
 
@@ -165,7 +167,7 @@ def cat_fms(reference_fm, target_fm, max_disp=192, start_disp=0, dilation=1):
     runs osa_cat_fms_f32 on the reference's own index list int(torch.linspace(start, end, n))."""
     ref, tgt = _f32c(_chk(reference_fm, "reference_fm", 4)), _f32c(_chk(target_fm, "target_fm", 4))
     if start_disp == 0 and dilation == 1:
-        return _build(None, None, 0, ref, tgt, max_disp, NCDHW)
+        return build_concat_volume(ref, tgt, max_disp)
     B, C, H, W = ref.shape
     n = (max_disp + dilation - 1) // dilation                                          # psmnet_cost_processor.py:31-33
     idx = torch.tensor([int(i) for i in torch.linspace(start_disp, start_disp + max_disp - 1, n)], dtype=torch.int32, device=ref.device)
@@ -224,7 +226,7 @@ def build_cost_volume_cl(gwc_left, gwc_right, num_groups, cat_left=None, cat_rig
         Cc = lc.shape[1]
     nch = num_groups + 2 * Cc
     VC = (nch + 3) // 4 * 4
-    return _build(lg, rg, num_groups, lc, rc, maxdisp, NDHWC, mask_left=mask_left, vol_channels=VC)
+    return _build(lg, rg, num_groups, lc, rc, maxdisp, mask_left=mask_left, vol_channels=VC)
 
 
 def build_cost_volume_from_cl(gwc_feat, num_groups, cat_feat, B, maxdisp, gwc_channels=None, cat_channels=None,
@@ -349,13 +351,10 @@ class FasterSoftArgmin(torch.nn.Module):
         if self.start_disp != 0 or self.dilation != 1:
             raise NotImplementedError("FasterSoftArgmin: only start_disp=0, dilation=1")
         c = cost_volume * self.alpha if self.alpha != 1.0 else cost_volume
-        if torch.is_grad_enabled() and c.requires_grad:          # training: forward + backward on the engine through autograd
-            from . import autograd as AG
-            out = AG.softmax_disparity_regression(c, keepdim=False) if self.normalize else AG.disparity_regression(c, c.shape[1], keepdim=False)
-            return out.to(cost_volume.dtype)
-        if self.normalize:
-            return softmax_disparity_regression(c, keepdim=False)
-        return disparity_regression(c, c.shape[1], keepdim=False)
+        out = softmax_disparity_regression(c, keepdim=False) if self.normalize else disparity_regression(c, c.shape[1], keepdim=False)
+        # one computation either way (both entries are differentiable); only the result dtype depends on the mode: training returns the
+        # volume's dtype, inference what the entry returns (fp32 for the fused softmax form)
+        return out.to(cost_volume.dtype) if (torch.is_grad_enabled() and c.requires_grad) else out
 
 
 def cl_rows(t: torch.Tensor):

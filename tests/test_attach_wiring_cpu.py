@@ -172,27 +172,38 @@ def test_reference_igev_hourglass(patched, sync_bn):
 
 @needs_ref
 def test_patched_functions_are_differentiable_dispatch(patched, monkeypatch):
-    """Under the patch the helpers route to the autograd Functions as soon as an argument requires grad (ADVICE r1:
-    the round-1 patch bound non-differentiable entries -> silent zero gradient into the backbone)."""
-    from openstereo_amd import attach, autograd as AG
+    """Under the patch the helpers route to the differentiable `ops` entries (the `osa_native` ops carry their own autograd kernels), with or
+    without an argument that requires grad: one call, and what it returns is part of the graph (the round-1 patch bound
+    non-differentiable entries -> silent zero gradient into the backbone)."""
+    from openstereo_amd import attach, ops
     attach.stub_reference_packages(REF)
     cv = importlib.import_module("stereo.modeling.cost_volume.cost_volume")
     calls = []
-    monkeypatch.setattr(AG, "build_gwc_volume", lambda l, r, d, g: calls.append("gwc") or (l[:, :g, None] * r[:, :g, None]).expand(-1, -1, d, -1, -1))
-    monkeypatch.setattr(AG, "disparity_regression", lambda x, d, keepdim=True: calls.append("reg") or x.sum(1, keepdim=keepdim))
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, "build_gwc_volume", lambda l, r, d, g: calls.append("gwc") or (l[:, :g, None] * r[:, :g, None]).expand(-1, -1, d, -1, -1))
+        mp.setattr(ops, "disparity_regression", lambda x, d, keepdim=True: calls.append("reg") or x.sum(1, keepdim=keepdim))
+        attach.patch_reference()
+        try:
+            l = torch.randn(1, 8, 4, 6, requires_grad=True)
+            v = cv.build_gwc_volume(l, torch.randn(1, 8, 4, 6), 3, 4)
+            assert calls == ["gwc"] and v.requires_grad
+            v.sum().backward()
+            assert l.grad is not None and float(l.grad.abs().sum()) > 0
+            dr = importlib.import_module("stereo.modeling.disp_pred.disp_regression")
+            p = torch.softmax(torch.randn(1, 5, 4, 6, requires_grad=True), 1)
+            out = dr.disparity_regression(p, 5)
+            assert calls == ["gwc", "reg"] and out.shape == (1, 1, 4, 6) and out.requires_grad
+            with torch.no_grad():
+                cv.build_gwc_volume(l, l, 3, 4)                           # no grad -> the same entry
+            assert calls == ["gwc", "reg", "gwc"]
+        finally:
+            attach.unpatch_reference()
     attach.patch_reference()
-    try:
-        l = torch.randn(1, 8, 4, 6, requires_grad=True)
-        v = cv.build_gwc_volume(l, torch.randn(1, 8, 4, 6), 3, 4)
-        assert calls == ["gwc"] and v.requires_grad
-        v.sum().backward()
-        assert l.grad is not None and float(l.grad.abs().sum()) > 0
-        dr = importlib.import_module("stereo.modeling.disp_pred.disp_regression")
-        p = torch.softmax(torch.randn(1, 5, 4, 6, requires_grad=True), 1)
-        out = dr.disparity_regression(p, 5)
-        assert calls == ["gwc", "reg"] and out.shape == (1, 1, 4, 6) and out.requires_grad
+    try:                                                                  # the real entry: the engine (GPU only), recording or not
+        with pytest.raises(Exception, match="no CPU path|engine"):
+            cv.build_gwc_volume(l, l, 3, 4)
         with torch.no_grad(), pytest.raises(Exception, match="no CPU path|engine"):
-            cv.build_gwc_volume(l, l, 3, 4)                           # no grad -> the non-recording engine entry (GPU only)
+            cv.build_gwc_volume(l, l, 3, 4)
     finally:
         attach.unpatch_reference()
 

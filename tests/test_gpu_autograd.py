@@ -819,3 +819,82 @@ def test_geo_lookup_accumulated_gradients_partial_backward_and_dense_form():
             assert float((x - y).abs().max()) <= 2e-6 * float(y.abs().max())
     again = run(True, (0, 1, 2))
     assert all(torch.equal(x, y) for x, y in zip(again, run(True, (0, 1, 2))))       # deterministic
+
+
+# ----------------------------------------------------------------------------- volumes / heads: one differentiable definition
+# The volume constructors and regression heads have no Python autograd.Function: `autograd.*` and `ops.*` are compositions over the
+# `osa_native` ops, differentiable in C++.  What the Functions they replaced computed is written out below (the forward op on fp32-contiguous
+# inputs, the explicit `*_bwd` op on the fp32 upstream gradient, a cast to the leaf's dtype) and must be reproduced bit for bit.
+# Result dtypes: recorded from one run, on the MI355X, of the last commit that had the Functions -- (input dtype, inside fp16 autocast) ->
+# result dtype.  The gradient that arrives at a leaf has the leaf's dtype in every row (recorded as well).
+_F32, _F16 = torch.float32, torch.float16
+_ALWAYS_F32 = {(_F32, False): _F32, (_F32, True): _F32, (_F16, False): _F32, (_F16, True): _F32}
+_INPUT_DTYPE = {(_F32, False): _F32, (_F32, True): _F32, (_F16, False): _F16, (_F16, True): _F16}
+VOLUME_HEAD_DTYPES = {
+    "AG.build_gwc_volume": _ALWAYS_F32, "AG.build_concat_volume": _ALWAYS_F32, "AG.build_concat_volume(mask_left=False)": _ALWAYS_F32,
+    "AG.correlation_volume": _ALWAYS_F32, "AG.softmax_disparity_regression": _ALWAYS_F32, "AG.upsample_softargmin": _ALWAYS_F32,
+    "AG.upsample_softargmin(5-D, align_corners)": _ALWAYS_F32,
+    # torch.sum of the reference's composition: the input's dtype, fp32 inside an autocast region
+    "AG.disparity_regression": {(_F32, False): _F32, (_F32, True): _F32, (_F16, False): _F16, (_F16, True): _F32},
+    "AG.disparity_regression(keepdim=False)": {(_F32, False): _F32, (_F32, True): _F32, (_F16, False): _F16, (_F16, True): _F32},
+    # the plain entries: no grad_fn before (so no gradient was recorded); result dtype as before, the gradient is the leaf's by autograd's rule
+    "ops.build_gwc_volume": _INPUT_DTYPE, "ops.build_concat_volume": _INPUT_DTYPE,
+}
+
+
+def _volume_head_cases():
+    """name -> (entry, inputs (fp32, CPU), old formula: (ns, fp32 inputs, fp32 upstream gradient) -> (fp32 result, [fp32 input gradients]))"""
+    from openstereo_amd import autograd as AG, ops
+    l, r = rn((2, 8, 5, 12), 41), rn((2, 8, 5, 12), 42)
+    prob, cost = F.softmax(rn((2, 12, 5, 7), 43, 2.0), 1), rn((2, 12, 5, 7), 44, 2.0)
+    shp = [2, 8, 5, 12]
+    gwc = lambda ns, i, g: (ns.gwc_volume(i[0], i[1], 6, 4), list(ns.volume_bwd(g, i[0], i[1], shp, 6, 4, False, True)))
+    cat = lambda m: lambda ns, i, g: (ns.concat_volume(i[0], i[1], 6, m), list(ns.volume_bwd(g, None, None, shp, 6, 0, True, m)))
+    corr = lambda ns, i, g: (ns.gwc_volume(i[0], i[1], 6, 1)[:, 0], list(ns.volume_bwd(g.unsqueeze(1), i[0], i[1], shp, 6, 1, False, True)))
+    reg = lambda keep: lambda ns, i, g: ((ns.softargmin(i[0]).unsqueeze(1) if keep else ns.softargmin(i[0])),
+                                         [ns.softargmin_bwd(g[:, 0] if keep else g, 12)])
+    sreg = lambda ns, i, g: (ns.softmax_softargmin(i[0], False)[0].unsqueeze(1), [ns.softmax_softargmin_bwd(i[0], g[:, 0])])
+    up = lambda al: lambda ns, i, g: (ns.upsample_softargmin(i[0], 24, 10, 14, al), [ns.upsample_softargmin_bwd(i[0], g, 24, 10, 14, al)])
+    return {
+        "AG.build_gwc_volume": (lambda a, b: AG.build_gwc_volume(a, b, 6, 4), (l, r), gwc),
+        "AG.build_concat_volume": (lambda a, b: AG.build_concat_volume(a, b, 6), (l, r), cat(True)),
+        "AG.build_concat_volume(mask_left=False)": (lambda a, b: AG.build_concat_volume(a, b, 6, False), (l, r), cat(False)),
+        "AG.correlation_volume": (lambda a, b: AG.correlation_volume(a, b, 6), (l, r), corr),
+        "AG.disparity_regression": (lambda p: AG.disparity_regression(p, 12), (prob,), reg(True)),
+        "AG.disparity_regression(keepdim=False)": (lambda p: AG.disparity_regression(p, 12, False), (prob,), reg(False)),
+        "AG.softmax_disparity_regression": (lambda c: AG.softmax_disparity_regression(c), (cost,), sreg),
+        "AG.upsample_softargmin": (lambda c: AG.upsample_softargmin(c, 24, 10, 14), (cost,), up(False)),
+        "AG.upsample_softargmin(5-D, align_corners)": (lambda c: AG.upsample_softargmin(c[:, None], 24, 10, 14, True), (cost,), up(True)),
+        "ops.build_gwc_volume": (lambda a, b: ops.build_gwc_volume(a, b, 6, 4), (l, r), gwc),
+        "ops.build_concat_volume": (lambda a, b: ops.build_concat_volume(a, b, 6), (l, r), cat(True)),
+    }
+
+
+@pytest.mark.parametrize("autocast", [False, True], ids=["plain", "autocast"])
+@pytest.mark.parametrize("dt", [_F32, _F16], ids=["fp32", "fp16"])
+def test_volume_and_head_entries_match_the_formulas_they_replaced(dt, autocast):
+    from openstereo_amd import _ext
+    ns = _ext.load()
+    cases = _volume_head_cases()
+    assert set(cases) == set(VOLUME_HEAD_DTYPES)
+    for name, (entry, inputs, old) in cases.items():
+        want_dt = VOLUME_HEAD_DTYPES[name][(dt, autocast)]
+        leaves = [t.to(DEV, dt).requires_grad_() for t in inputs]
+        with torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
+            out = entry(*leaves)
+        print(f"{name} {dt} autocast={autocast}: result {out.dtype}, grad_fn {type(out.grad_fn).__name__}")
+        assert out.dtype == want_dt, f"{name}: result {out.dtype}, recorded {want_dt}"
+        assert out.grad_fn is not None, f"{name}: the result of inputs that require grad carries no grad_fn"
+        g = rn(tuple(out.shape), 45).to(DEV, out.dtype)
+        out.backward(g)
+        in32 = [t.detach().float().contiguous() for t in leaves]
+        ref, grads = old(ns, in32, g.float())
+        assert torch.equal(out.detach(), ref.to(want_dt)), f"{name}: forward differs from the forward op on fp32 inputs"
+        for t, gr in zip(leaves, grads):
+            print(f"    leaf {t.dtype}: grad {t.grad.dtype}")
+            assert t.grad.dtype == dt, f"{name}: gradient {t.grad.dtype} at a {dt} leaf"
+            assert torch.equal(t.grad, gr.to(dt)), f"{name}: gradient differs from the explicit backward op"
+        if name.startswith("AG."):                       # not recording: the same values, nothing kept for a backward pass
+            with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16, enabled=autocast):
+                quiet = entry(*leaves)
+            assert quiet.grad_fn is None and not quiet.requires_grad and quiet.dtype == want_dt and torch.equal(quiet, out.detach()), name

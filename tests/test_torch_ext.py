@@ -51,6 +51,37 @@ def test_no_package_module_launches_through_ctypes():
     assert not offenders, offenders
 
 
+def test_volume_and_head_gradients_are_defined_once():
+    """The six volume / regression-head ops are differentiable in C++ (TORCH_LIBRARY_IMPL(osa_native, Autograd)): the package's Python holds
+    no second copy of their gradients -- no autograd.Function for them, no call of their `*_bwd` ops outside torch_ops.py (the public
+    `torch.ops.openstereo_amd.*` registration) -- and the batched weight-gradient launch of the conv Functions is written once."""
+    import ast
+    files = sorted(glob.glob(os.path.join(ROOT, "openstereo_amd", "**", "*.py"), recursive=True))
+    texts = {os.path.relpath(p, ROOT): open(p).read() for p in files}
+    tree = ast.parse(texts["openstereo_amd/autograd.py"])
+    classes = {n.name for n in ast.walk(tree) if isinstance(n, ast.ClassDef)}
+    assert not classes & {"_GwcVolume", "_ConcatVolume", "_SoftArgmin", "_SoftmaxSoftArgmin", "_UpsampleSoftArgmin"}
+    import re
+    bwd_op = re.compile(r"(?<![A-Za-z0-9_])(volume_bwd|softargmin_bwd|softmax_softargmin_bwd|upsample_softargmin_bwd)(?![A-Za-z0-9_])")
+    offenders = [f"{name}: {m.group(0)}" for name, text in texts.items() if os.path.basename(name) != "torch_ops.py" for m in bwd_op.finditer(text)]
+    assert not offenders, offenders                  # (whole names: the C symbols `osa_*_bwd_f32` in _lib.py's declaration table are not meant)
+
+    def calls_wgrad(fn):
+        return any(isinstance(c, ast.Call) and isinstance(c.func, ast.Name) and c.func.id == "_wgrad" for c in ast.walk(fn))
+    callers = set()
+    for node in ast.walk(tree):                      # functions whose own body (nested lambdas / closures included) calls _wgrad(...)
+        if isinstance(node, ast.ClassDef):
+            callers |= {f"{node.name}.{f.name}" for f in node.body if isinstance(f, ast.FunctionDef) and calls_wgrad(f)}
+    callers |= {f.name for f in tree.body if isinstance(f, ast.FunctionDef) and calls_wgrad(f)}
+    assert callers <= {"_wgrad_items", "_ConvTranspose3d.backward"}, callers
+    from openstereo_amd import autograd as AG
+    for name in ("build_gwc_volume", "build_concat_volume", "correlation_volume", "disparity_regression", "softmax_disparity_regression",
+                 "upsample_softargmin"):             # the entries a caller may rebind on the module: the models reach them as AG.<name>
+        assert callable(getattr(AG, name)), name
+    # the package's Python before the Python twins of these gradients were removed: 6881 lines
+    assert sum(t.count("\n") for t in texts.values()) < 6881
+
+
 def test_variant_directory_binds_the_extension_to_its_own_library(lib, tmp_path):
     """An A/B variant (tools/build_variant.sh) is a directory holding its libopenstereo_amd.so and a copy of libosa_torch_ext.so; with
     OSA_LIB_PATH pointing into it, the extension loads from there and binds to the library beside it, not to the shipped one.  CPU only:
