@@ -563,8 +563,10 @@ int osa_geo_lookup_bwd_f32(float* const* dgeo_levels, float* const* dcorr_levels
                            const float* disp, const float* coords_x, const float* dout,
                            int B, int H, int W, int C, int radius, void* stream);
 /* The same gradient ACCUMULATED into dgeo_levels / dcorr_levels (r6): the caller zero-fills them once per training step and calls this for
- * every lookup of the step (one per GRU iteration, igev_stereo.py:181-203); only the (C+1) x (2r+2) entries per (pixel, level) a lookup's
- * taps reach are touched (read-modify-write, no atomics: a pixel owns its rows) -- instead of 22 dense gradients that autograd adds up. */
+ * every lookup of the step (one per GRU iteration, igev_stereo.py:181-203); only the entries a lookup's taps reach, inside a window of 2r+3
+ * positions per row of a (pixel, level), are touched (read-modify-write, no atomics: one lane per position, which sums its taps in ascending
+ * order -- into zeros the result equals osa_geo_lookup_bwd_f32 bit for bit) -- instead of 22 dense gradients that autograd adds up.
+ * radius <= 30, level lengths <= 2^19. */
 int osa_geo_lookup_bwd_acc_f32(float* const* dgeo_levels, float* const* dcorr_levels,
                                const int* geo_len, const int* corr_len, int levels,
                                const float* disp, const float* coords_x, const float* dout,

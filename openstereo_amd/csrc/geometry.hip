@@ -376,46 +376,64 @@ __global__ __launch_bounds__(256) void geo_lookup_bwd_rows_kernel(const LookupBw
 
 // Accumulating form (r6): the reference's loop looks the SAME pyramid up once per GRU iteration (igev_stereo.py:181-203: 22 iterations in
 // training), so autograd used to receive 22 dense gradients per level (50 MB each at the 320x736 crop, 98 % zeros) and add them up.  Here
-// the level gradients are accumulators the caller zero-fills once per step; a lookup's backward touches only the (C + 1) x (taps + 1)
-// entries per (pixel, level) its taps reach: one thread per entry, a read-modify-write without atomics (every pixel owns its rows, and
-// the entries of one row are distinct positions) -- 2.6 M entries instead of 12.5 M written and 12.5 M added per iteration.
+// the level gradients are accumulators the caller zero-fills once per step; a lookup's backward touches only the window of 2r + 3 positions
+// per row of a (pixel, level) that its taps can reach: one lane per position, a read-modify-write without atomics (every pixel owns its
+// rows, a lane owns its position) -- 2.6 M entries touched instead of 12.5 M written and 12.5 M added per iteration.
+//
+// Which position a tap reaches is tap_of()'s business alone.  Its float round trip returns an integer position k as k - eps or k + eps,
+// and dx + x rounds differently from tap to tap, so consecutive taps do NOT always have consecutive x0: the step is 0 ("both taps reach
+// the same two positions") or 2 ("the position between them belongs to the first tap alone") at a few per cent of the lattice positions.
+// (The first version of this kernel took entry jj to be position x0(tap jj) = x0(tap jj - 1) + 1: it dropped the w1 term of the tap before
+// a step of 2 and let two lanes add to one address at a step of 0.)  So the window is anchored once per row: lane e of a row owns position
+// x0(tap 0) + e, e = 0 .. 2r + 2, and adds up, in ascending tap order (the order of the dense kernels: into zeros the result is theirs bit
+// for bit), the w0 terms of the taps whose x0 is its position and the w1 terms of those whose x0 + 1 is.
+// Why that window holds every term: tap k samples fl(dx_k + x) and tap_of() moves it by at most u * (4 |x| + n) (u = 2^-24; one rounding
+// each in 2x / (n - 1), - 1, + 1, * (n - 1)), together under 0.4 for |x|, n <= 2^20 (host: n <= 2^19; farther out every tap is off the row
+// and nothing is stored).  With every ix_k within 0.5 of x + dx_k and ix non-decreasing in k, x0(tap k) - x0(tap 0) is k - 1, k or k + 1:
+// positions x0(tap 0) .. x0(tap 0) + 2r + 2, and position x0(tap 0) + e can only be reached by taps e - 2 .. e + 1.
+// Lanes: a row takes G = 2r + 3 consecutive lanes of a wave, 64 / G rows per wave (5 of the 9-tap rows: 55 lanes).  Lane e < 2r + 1 evaluates
+// tap e and loads its upstream gradient -- once per tap -- and the lanes of a row exchange (x0, g * w0, g * w1) by shuffles.
+template <int TAPS>      // TAPS = 2 * radius + 1 known at compile time (9 in every shipped config), 0 = generic
 __global__ __launch_bounds__(256) void geo_lookup_bwd_acc_kernel(const LookupBwdGatherArgs p) {
-    const long long HW = (long long)p.H * p.W;
-    const int taps = 2 * p.radius + 1;
-    const int per_px = (p.C + 1) * (taps + 1);
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned HW = (unsigned)p.H * p.W;
+    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
+    const int G = taps + 2;                                              // <= 64 (host)
+    const int rpw = 64 / G;                                              // rows per wave
+    const unsigned nrows = (unsigned)p.B * HW * (p.C + 1);               // host: < 2^31
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);          // host: waves * rpw < 2^32
     const int l = blockIdx.y;
-    if (t >= (long long)p.B * HW * per_px) return;
-    const long long i = t / per_px;                                      // pixel
-    const int e = (int)(t - i * per_px);
-    const int c = e / (taps + 1), jj = e - c * (taps + 1);               // row (c == C: the correlation row), entry of the tap window
-    const long long b = i / HW, hw = i - b * HW;
-    float scale = 1.f;
-    for (int q = 0; q < l; ++q) scale *= 0.5f;
+    const int rw = lane / G, e = lane - rw * G;
+    const unsigned R = wave * (unsigned)rpw + rw;
+    const bool row_on = rw < rpw && R < nrows;                           // (no early return: every lane takes part in the shuffles)
+    const unsigned Rc = row_on ? R : 0u;
+    const unsigned i = Rc / (unsigned)(p.C + 1);                         // pixel
+    const int c = (int)(Rc - i * (unsigned)(p.C + 1));                   // row (c == C: the correlation row)
+    const unsigned b = i / HW, hw = i - b * HW;
+    const float scale = 1.f / (float)(1 << l);                          // exact: the dense kernels multiply 0.5f l times
     const float d = p.disp[i], cx = p.coords[i];
     const bool geo = c < p.C;
     const float x = geo ? d * scale : cx * scale - d * scale;
     const int n = geo ? p.Dl[l] : p.Wl[l];
     const int per_level = (p.C + 1) * taps;
     const float* o = p.dout + (size_t)b * per_level * p.levels * HW + hw + ((size_t)l * per_level + (size_t)c * taps) * HW;
-    // entry jj is position x0(tap jj) (= x0(tap jj - 1) + 1): tap jj - 1 reaches it with its w1, tap jj with its w0 -- the order in which
-    // the dense kernels add them
+    const Tap tk = tap_of((float)(e - taps / 2) + x, n);                 // (lanes e >= taps: evaluated, never used)
+    const float ov = (row_on && e < taps) ? o[(size_t)e * HW] : 0.f;
+    const int x0 = tk.x0;
+    const float t0 = ov * tk.w0, t1 = ov * tk.w1;
+    const int j = __shfl(x0, lane - e) + e;                              // this lane's position
     float v = 0.f;
-    int j;
-    if (jj < taps) {
-        const Tap tk = tap_of((float)(jj - p.radius) + x, n);
-        j = tk.x0;
-        if (jj >= 1) {
-            const Tap tp = tap_of((float)(jj - 1 - p.radius) + x, n);
-            if (tp.x0 + 1 == j) v += o[(size_t)(jj - 1) * HW] * tp.w1;
-        }
-        v += o[(size_t)jj * HW] * tk.w0;
-    } else {
-        const Tap tp = tap_of((float)(jj - 1 - p.radius) + x, n);
-        j = tp.x0 + 1;
-        v += o[(size_t)(jj - 1) * HW] * tp.w1;
+    bool hit = false;
+#pragma unroll
+    for (int q = -2; q <= 1; ++q) {                                      // taps e - 2 .. e + 1 of this row, ascending
+        const int src = (lane + q) & 63;
+        const int xs = __shfl(x0, src);
+        const float a0 = __shfl(t0, src), a1 = __shfl(t1, src);
+        const bool on = e + q >= 0 && e + q < taps;                      // (then lane + q is a lane of this row)
+        if (on && xs == j) { v += a0; hit = true; }
+        if (on && xs + 1 == j) { v += a1; hit = true; }
     }
-    if (j < 0 || j >= n) return;
+    if (!row_on || !hit || j < 0 || j >= n) return;
     float* dst = geo ? p.dgeo[l] + ((size_t)i * p.C + c) * n + j : p.dcorr[l] + (size_t)i * n + j;
     *dst += v;
 }
@@ -482,9 +500,16 @@ extern "C" int osa_geo_lookup_bwd_acc_f32(float* const* dgeo_levels, float* cons
     }
     g.disp = disp; g.coords = coords_x; g.dout = dout;
     g.B = B; g.H = H; g.W = W; g.C = C; g.levels = levels; g.radius = radius;
-    const long long n = (long long)B * H * W * (C + 1) * (2 * radius + 2);
-    OSA_REQUIRE((n + 255) / 256 < (1ll << 31), "geo_lookup_bwd_acc: grid too large");
-    hipLaunchKernelGGL(geo_lookup_bwd_acc_kernel, dim3((unsigned)((n + 255) / 256), levels), dim3(256), 0, (hipStream_t)stream, g);
+    OSA_REQUIRE(radius <= 30, "geo_lookup_bwd_acc: radius %d: a row's window of 2r + 3 positions has to fit a wave", radius);
+    for (int l = 0; l < levels; ++l)
+        OSA_REQUIRE(geo_len[l] <= (1 << 19) && corr_len[l] <= (1 << 19), "geo_lookup_bwd_acc: level %d longer than 2^19", l);
+    const long long nrows = (long long)B * H * W * (C + 1);
+    const int rpw = 64 / (2 * radius + 3);                                  // rows per wave
+    const long long waves = (nrows + rpw - 1) / rpw;
+    OSA_REQUIRE(nrows > 0 && nrows < (1ll << 31) && (waves + 3) / 4 < (1ll << 30), "geo_lookup_bwd_acc: grid too large");
+    const dim3 grid((unsigned)((waves + 3) / 4), levels);
+    if (radius == 4) hipLaunchKernelGGL(geo_lookup_bwd_acc_kernel<9>, grid, dim3(256), 0, (hipStream_t)stream, g);
+    else hipLaunchKernelGGL(geo_lookup_bwd_acc_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, g);
     OSA_LAUNCH_CHECK("geo_lookup_bwd_acc");
     return 0;
 }
