@@ -32,6 +32,8 @@
  *   osa_upsample_softargmin_f32 F.interpolate(trilinear)+softmax+regression,
  *                               models/gwcnet/gwcnet_disp_processor.py:99-133,
  *                               models/psmnet/psmnet_cost_processor.py:201-214
+ *   osa_*softargmin_var_f32     the three heads with disparity_variance beside the disparity,
+ *                               models/cfnet/submodule.py:128-134, models/igevpp/submodule.py:153-159
  */
 #ifndef OPENSTEREO_AMD_H
 #define OPENSTEREO_AMD_H
@@ -42,7 +44,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 7
+#define OSA_ABI_VERSION 8
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -482,6 +484,22 @@ int osa_upsample_softargmin_f32(const float* cost_lowres, float* out,
                                 int B, int Dl, int Hl, int Wl, int D, int H, int W,
                                 int align_corners, void* stream);
 
+/* ---- disparity + per-pixel variance of the distribution (ABI v8) -------- */
+/* The three heads above with a second result, var[b,h,w] = sum_d p_d (d - disparity)^2 (the reference's disparity_variance).  `out` of
+ * each entry holds the bits the entry without `_var` writes for the same input; the variance is accumulated about the mean, never as
+ * E[d^2] - E[d]^2.
+ * probabilities form: the disparity map is GIVEN ([B,H,W]; it need not be prob's mean and prob need not be normalised);
+ * out[b,h,w] = sum_d d * prob (may be NULL). */
+int osa_softargmin_var_f32(const float* prob, const float* disparity, float* out, float* var,
+                           int B, int D, int H, int W, void* stream);
+/* logits form: p = softmax_d(cost), out = sum_d d p_d, var = sum_d p_d (d - out)^2 */
+int osa_softmax_softargmin_var_f32(const float* cost, float* out, float* var,
+                                   int B, int D, int H, int W, void* stream);
+/* fused form: the samples of osa_upsample_softargmin_f32 (same path choice: x4 streaming kernel or the generic LDS kernel) */
+int osa_upsample_softargmin_var_f32(const float* cost_lowres, float* out, float* var,
+                                    int B, int Dl, int Hl, int Wl, int D, int H, int W,
+                                    int align_corners, void* stream);
+
 /* ---- backward of the memory-bound ops (training) ------- */
 /* d(build_gwc_volume) (concat=0: left/right = forward features [B,C,H,W]) or d(build_concat_volume)
  * (concat=1: C = channels per side).  dvol is NCDHW with vol_channels channels; this op's channels
@@ -508,6 +526,18 @@ size_t osa_upsample_softargmin_bwd_workspace_bytes(int B, int Dl, int H, int W);
 int osa_upsample_softargmin_bwd_ws_f32(const float* cost_lowres, const float* dout, float* dcost_lowres,
                                        int B, int Dl, int Hl, int Wl, int D, int H, int W,
                                        int align_corners, void* workspace, size_t workspace_bytes, void* stream);
+/* Backward of the disparity + variance heads (ABI v8): dout / dvar are the gradients of `out` / `var`, [B,H,W] each.  Atomic-free,
+ * deterministic.
+ * dprob[d] = d * dout + (d - disparity)^2 * dvar;  ddisparity = -2 dvar sum_d prob[d] (d - disparity).  dout may be NULL (zero). */
+int osa_softargmin_var_bwd_f32(const float* prob, const float* disparity, const float* dout, const float* dvar,
+                               float* dprob, float* ddisparity, int B, int D, int H, int W, void* stream);
+/* dcost[k] = p_k * ((k - disp) * dout + ((k - disp)^2 - var) * dvar) */
+int osa_softmax_softargmin_var_bwd_f32(const float* cost, const float* dout, const float* dvar, float* dcost,
+                                       int B, int D, int H, int W, void* stream);
+/* the same coefficient through the two-pass form of osa_upsample_softargmin_bwd_ws_f32 (same workspace size query) */
+int osa_upsample_softargmin_var_bwd_ws_f32(const float* cost_lowres, const float* dout, const float* dvar, float* dcost_lowres,
+                                           int B, int Dl, int Hl, int Wl, int D, int H, int W,
+                                           int align_corners, void* workspace, size_t workspace_bytes, void* stream);
 
 /* max |x| over n contiguous floats (16-byte aligned) folded into the range block `meta` (osa_f16x3_ranges layout: 8 slots, atomic max) --
  * the device-side operand range of a tensor that reaches an f16x3 layer from outside the engine (what torch.linalg.vector_norm(x, inf)

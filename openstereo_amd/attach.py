@@ -235,6 +235,7 @@ def _graft_plan():
                                               "PSMAggregator": (PSM.PSMAggregator, fwd + ("aggregate_cl", "aggregate_train"), False),   # :182-221
                                               "PSMCostProcessor": (PSM.PSMCostProcessor, ("forward",), False)}),
         (M + "psmnet.psmnet_disp_processor", {"PSMDispProcessor": (PSM.PSMDispProcessor, ("forward",), False)}),
+        (M + "psmnet.psmnet", {"PSMNet": (PSM.PSMNet, ("forward",), False)}),                                  # psmnet.py:20-29 (the same three stage calls; carries return_variance)
         (M + "psmnet.psmnet_backbone", {"PSMNet": (PSM.PSMBackbone, ("forward", "forward_cl", "_pack", "reset_engine", "use_engine"), False)}),
         (M + "stereobase.igev_blocks", {"FeatureAtt": (IG.FeatureAtt, ("logits",), False)}),
         (M + "stereobase.hourglass", {"Hourglass": (IG.Hourglass, fwd + ("gate_logits", "_unit_train"), False)}),   # hourglass.py:79-104

@@ -3,7 +3,7 @@
 Forward AND backward of everything here run on the engine's HIP kernels:
   * volume constructors  -> osa_build_volume_f32 / osa_build_volume_bwd_f32
   * regression heads     -> osa_*softargmin*_f32 / *_bwd_f32
-    These six entries hold no gradient code: they are compositions over the `osa_native` ops, which are
+    These entries hold no gradient code: they are compositions over the `osa_native` ops, which are
     differentiable in C++ (csrc/torch_ext.cpp registers their Autograd kernels) -- one definition, shared
     with `openstereo_amd.ops` and `openstereo_amd.attach`.
   * Conv3d / ConvTranspose3d / Conv2d -> torch.autograd.Functions: the MFMA implicit-GEMM kernel (forward),
@@ -70,6 +70,21 @@ def softmax_disparity_regression(cost, keepdim=True):
 def upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners=False):
     """-> fp32 [B, h, w]"""
     return ops.upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners)
+
+
+def disparity_variance(prob, maxdisp, disparity):
+    """-> [B, 1, H, W] in the promoted input dtype; fp32 inside an autocast region.  Gradients reach `prob` and `disparity`."""
+    return ops.disparity_variance(prob, maxdisp, disparity)
+
+
+def softmax_disparity_regression_variance(cost, keepdim=True):
+    """-> (disp, var), fp32"""
+    return ops.softmax_disparity_regression(cost, keepdim=keepdim, return_variance=True)
+
+
+def upsample_softargmin_variance(cost_lowres, maxdisp, h, w, align_corners=False):
+    """-> (disp, var), fp32 [B, h, w] each"""
+    return ops.upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners, return_variance=True)
 
 
 # ----------------------------------------------------------------------------- convolutions

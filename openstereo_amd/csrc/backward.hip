@@ -242,6 +242,122 @@ __global__ __launch_bounds__(256) void upsample_softargmin_bwd_gather_kernel(con
     p.dcost[i] = acc;
 }
 
+// ---- backward of the disparity + variance heads (softargmin.hip) ------------------------------------------------------------------------
+// Two incoming gradients per pixel: g of the disparity, gv of the variance.  One thread per pixel, serial over d: no atomics, fixed order.
+//  probabilities + given disparity `delta`:  dprob[d] = d g + (d - delta)^2 gv;   ddelta = -2 gv sum_d prob[d] (d - delta)
+//  logits (p = softmax, mu = sum p d, var = sum p (d - mu)^2):
+//                                            dcost[k] = p_k [ (k - mu) g + ((k - mu)^2 - var) gv ]
+//  (the variance's dependence on its own mean drops out: sum_d p_d (d - mu) = 0)
+__global__ __launch_bounds__(256) void softargmin_var_bwd_kernel(const float* __restrict__ prob, const float* __restrict__ disparity,
+                                                                 const float* __restrict__ dout, const float* __restrict__ dvar,
+                                                                 float* __restrict__ dprob, float* __restrict__ ddisp,
+                                                                 int D, long long HW, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;    // over B*H*W
+    if (i >= total) return;
+    const long long b = i / HW, hw = i - b * HW;
+    const float* p = prob + (size_t)b * D * HW + hw;
+    float* dp = dprob + (size_t)b * D * HW + hw;
+    // fp64 arithmetic, one rounding per result: the kernel is bound by its two D-plane streams, and d - delta, its square and the sum each
+    // cost an fp32 rounding that the reference's own fp32 autograd (the test's yardstick, ~1 ulp) leaves no room for
+    const double mu = disparity[i], g = dout ? dout[i] : 0.f, gv = dvar[i];
+    double s = 0.0;
+#pragma unroll 8
+    for (int d = 0; d < D; ++d) {
+        const double t = (double)d - mu;
+        s = fma((double)p[(size_t)d * HW], t, s);
+        dp[(size_t)d * HW] = (float)fma((double)d, g, t * t * gv);
+    }
+    ddisp[i] = (float)(-2.0 * gv * s);
+}
+
+__global__ __launch_bounds__(256) void softmax_softargmin_var_bwd_kernel(const float* __restrict__ cost, const float* __restrict__ dout,
+                                                                         const float* __restrict__ dvar, float* __restrict__ dcost,
+                                                                         int D, long long HW, long long total) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;    // over B*H*W
+    if (i >= total) return;
+    const long long b = i / HW, hw = i - b * HW;
+    const float* c = cost + (size_t)b * D * HW + hw;
+    float m = -INFINITY;
+    for (int d = 0; d < D; ++d) m = fmaxf(m, c[(size_t)d * HW]);
+    float se = 0.f, sd = 0.f;
+    for (int d = 0; d < D; ++d) { const float e = expf(c[(size_t)d * HW] - m); se += e; sd = fmaf(e, (float)d, sd); }
+    const float inv = 1.f / se, disp = sd * inv, g = dout[i], gv = dvar[i];
+    float sv = 0.f;
+    for (int d = 0; d < D; ++d) { const float t = (float)d - disp; sv = fmaf(expf(c[(size_t)d * HW] - m), t * t, sv); }
+    const float var = sv * inv;
+    float* dc = dcost + (size_t)b * D * HW + hw;
+    for (int d = 0; d < D; ++d) {
+        const float t = (float)d - disp;
+        dc[(size_t)d * HW] = expf(c[(size_t)d * HW] - m) * inv * fmaf(t * t - var, gv, t * g);
+    }
+}
+
+struct UpVarBwdArgs {
+    UpBwdArgs a;
+    const float* dvar;
+};
+
+// pass 1 of the two-pass form with the variance's gradient: upsample_softargmin_bwd_fold_kernel with the per-sample coefficient of the
+// logits form above (one more pass over the LDS-resident samples for the variance).  Pass 2 is upsample_softargmin_bwd_gather_kernel.
+template <int NT>
+__global__ __launch_bounds__(NT) void upsample_softargmin_var_bwd_fold_kernel(const UpVarBwdArgs q, float* __restrict__ G) {
+    extern __shared__ float sh[];            // cl[Dl][NT] then gl[Dl][NT]
+    const UpBwdArgs& p = q.a;
+    float* cl = sh; float* gl = sh + (size_t)p.Dl * NT;
+    const int tid = threadIdx.x;
+    const long long HW = (long long)p.H * p.W;
+    const long long i = (long long)blockIdx.x * NT + tid;
+    const bool live = i < (long long)p.B * HW;
+    const long long ii = live ? i : 0;
+    const int b = (int)(ii / HW);
+    const int hw = (int)(ii - (long long)b * HW);
+    const int y = hw / p.W, x = hw - y * p.W;
+    int y0, y1, x0, x1; float ly, lx;
+    src_index_b(y, p.sh, p.align, p.Hl, y0, y1, ly);
+    src_index_b(x, p.sw, p.align, p.Wl, x0, x1, lx);
+    const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
+    const size_t plane = (size_t)p.Hl * p.Wl;
+    const float* c = p.cost + (size_t)b * p.Dl * plane;
+    const size_t o00 = (size_t)y0 * p.Wl + x0, o01 = (size_t)y0 * p.Wl + x1, o10 = (size_t)y1 * p.Wl + x0, o11 = (size_t)y1 * p.Wl + x1;
+    float m = -INFINITY;
+    for (int dl = 0; dl < p.Dl; ++dl) {
+        const float* cp = c + (size_t)dl * plane;
+        const float v = w00 * cp[o00] + w01 * cp[o01] + w10 * cp[o10] + w11 * cp[o11];
+        cl[dl * NT + tid] = v; gl[dl * NT + tid] = 0.f;
+        m = fmaxf(m, v);
+    }
+    float se = 0.f, sdisp = 0.f;
+    for (int d = 0; d < p.D; ++d) {
+        int d0, d1; float ld;
+        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
+        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);
+        se += e; sdisp = fmaf(e, (float)d, sdisp);
+    }
+    const float inv = 1.f / se, disp = sdisp * inv;
+    float sv = 0.f;
+    for (int d = 0; d < p.D; ++d) {
+        int d0, d1; float ld;
+        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
+        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);
+        const float t = (float)d - disp;
+        sv = fmaf(e, t * t, sv);
+    }
+    const float var = sv * inv;
+    const float g = live ? p.dout[i] : 0.f, gv = live ? q.dvar[i] : 0.f;
+    for (int d = 0; d < p.D; ++d) {
+        int d0, d1; float ld;
+        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
+        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);
+        const float t = (float)d - disp;
+        const float gd = e * inv * fmaf(t * t - var, gv, t * g);
+        gl[d0 * NT + tid] += (1.f - ld) * gd;
+        gl[d1 * NT + tid] += ld * gd;
+    }
+    if (!live) return;
+    float* gp = G + (size_t)b * p.Dl * HW + hw;
+    for (int dl = 0; dl < p.Dl; ++dl) gp[(size_t)dl * HW] = gl[dl * NT + tid];
+}
+
 }  // namespace osa
 
 using namespace osa;
@@ -339,5 +455,56 @@ extern "C" int osa_upsample_softargmin_bwd_ws_f32(const float* cost_lowres, cons
     OSA_LAUNCH_CHECK("upsample_softargmin_bwd_ws (fold)");
     hipLaunchKernelGGL(upsample_softargmin_bwd_gather_kernel, dim3(cdiv((long long)B * Dl * Hl * Wl, 256)), dim3(256), 0, st, a, (const float*)G);
     OSA_LAUNCH_CHECK("upsample_softargmin_bwd_ws (gather)");
+    return 0;
+}
+
+// ---- disparity + variance heads ---------------------------------------------------------------------------------------------------
+extern "C" int osa_softargmin_var_bwd_f32(const float* prob, const float* disparity, const float* dout, const float* dvar,
+                                          float* dprob, float* ddisparity, int B, int D, int H, int W, void* stream) {
+    OSA_REQUIRE(prob && disparity && dvar && dprob && ddisparity, "softargmin_var_bwd: NULL pointer");     // dout may be NULL: no disparity gradient
+    OSA_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "softargmin_var_bwd: bad dims");
+    const long long HW = (long long)H * W, total = HW * B;
+    hipLaunchKernelGGL(softargmin_var_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       prob, disparity, dout, dvar, dprob, ddisparity, D, HW, total);
+    OSA_LAUNCH_CHECK("softargmin_var_bwd");
+    return 0;
+}
+
+extern "C" int osa_softmax_softargmin_var_bwd_f32(const float* cost, const float* dout, const float* dvar, float* dcost,
+                                                  int B, int D, int H, int W, void* stream) {
+    OSA_REQUIRE(cost && dout && dvar && dcost, "softmax_softargmin_var_bwd: NULL pointer");
+    OSA_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "softmax_softargmin_var_bwd: bad dims");
+    const long long HW = (long long)H * W, total = HW * B;
+    hipLaunchKernelGGL(softmax_softargmin_var_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       cost, dout, dvar, dcost, D, HW, total);
+    OSA_LAUNCH_CHECK("softmax_softargmin_var_bwd");
+    return 0;
+}
+
+extern "C" int osa_upsample_softargmin_var_bwd_ws_f32(const float* cost_lowres, const float* dout, const float* dvar, float* dcost_lowres,
+                                                      int B, int Dl, int Hl, int Wl, int D, int H, int W,
+                                                      int align_corners, void* workspace, size_t workspace_bytes, void* stream) {
+    OSA_REQUIRE(cost_lowres && dout && dvar && dcost_lowres && workspace, "upsample_softargmin_var_bwd_ws: NULL pointer");
+    OSA_REQUIRE(B > 0 && Dl > 0 && Hl > 0 && Wl > 0 && D > 0 && H > 0 && W > 0, "upsample_softargmin_var_bwd_ws: bad dims");
+    OSA_REQUIRE(workspace_bytes >= osa_upsample_softargmin_bwd_workspace_bytes(B, Dl, H, W) && ((size_t)workspace & 15) == 0,
+                "upsample_softargmin_var_bwd_ws: workspace too small or misaligned (osa_upsample_softargmin_bwd_workspace_bytes)");
+    constexpr int NT = 128;
+    const size_t lds = (size_t)Dl * NT * sizeof(float) * 2;
+    OSA_REQUIRE(lds <= 160 * 1024, "upsample_softargmin_var_bwd_ws: Dl=%d too large for LDS", Dl);
+    UpVarBwdArgs q;
+    UpBwdArgs& a = q.a;
+    a.cost = cost_lowres; a.dout = dout; a.dcost = dcost_lowres;
+    a.B = B; a.Dl = Dl; a.Hl = Hl; a.Wl = Wl; a.D = D; a.H = H; a.W = W; a.align = align_corners ? 1 : 0;
+    auto sc = [&](int in, int out) { return a.align ? ((out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f) : (float)in / (float)out; };
+    a.sd = sc(Dl, D); a.sh = sc(Hl, H); a.sw = sc(Wl, W);
+    q.dvar = dvar;
+    hipStream_t st = (hipStream_t)stream;
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)upsample_softargmin_var_bwd_fold_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    float* G = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(upsample_softargmin_var_bwd_fold_kernel<NT>, dim3(cdiv((long long)B * H * W, NT)), dim3(NT), lds, st, q, G);
+    OSA_LAUNCH_CHECK("upsample_softargmin_var_bwd_ws (fold)");
+    hipLaunchKernelGGL(upsample_softargmin_bwd_gather_kernel, dim3(cdiv((long long)B * Dl * Hl * Wl, 256)), dim3(256), 0, st, a, (const float*)G);
+    OSA_LAUNCH_CHECK("upsample_softargmin_var_bwd_ws (gather)");
     return 0;
 }

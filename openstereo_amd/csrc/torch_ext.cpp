@@ -101,6 +101,38 @@ at::Tensor upsample_softargmin(const at::Tensor& cost_lowres, int64_t maxdisp, i
     return out;
 }
 
+// disparity + variance (reference: disparity_variance, models/cfnet/submodule.py:128-134 == models/igevpp/submodule.py:153-159)
+std::tuple<at::Tensor, at::Tensor> softargmin_var(const at::Tensor& prob, const at::Tensor& disparity) {
+    gpu_f32(prob, "prob"); gpu_f32(disparity, "disparity");
+    TORCH_CHECK(prob.dim() == 4, "softargmin_var: prob must be [B,D,H,W]");
+    const auto p = prob.contiguous(), d = disparity.contiguous();
+    TORCH_CHECK(d.numel() == p.size(0) * p.size(2) * p.size(3), "softargmin_var: disparity must be [B,1,H,W] or [B,H,W]");
+    auto out = at::empty({p.size(0), p.size(2), p.size(3)}, p.options()), var = at::empty_like(out);
+    OSA_CALL(osa_softargmin_var_f32(fp(p), fp(d), out.data_ptr<float>(), var.data_ptr<float>(), (int)p.size(0), (int)p.size(1), (int)p.size(2), (int)p.size(3),
+                                    cur_stream()));
+    return {out, var};
+}
+
+std::tuple<at::Tensor, at::Tensor> softmax_softargmin_var(const at::Tensor& cost) {
+    gpu_f32(cost, "cost");
+    TORCH_CHECK(cost.dim() == 4, "softmax_softargmin_var: cost must be [B,D,H,W]");
+    const auto c = cost.contiguous();
+    auto out = at::empty({c.size(0), c.size(2), c.size(3)}, c.options()), var = at::empty_like(out);
+    OSA_CALL(osa_softmax_softargmin_var_f32(fp(c), out.data_ptr<float>(), var.data_ptr<float>(), (int)c.size(0), (int)c.size(1), (int)c.size(2), (int)c.size(3),
+                                            cur_stream()));
+    return {out, var};
+}
+
+std::tuple<at::Tensor, at::Tensor> upsample_softargmin_var(const at::Tensor& cost_lowres, int64_t maxdisp, int64_t h, int64_t w, bool align_corners) {
+    gpu_f32(cost_lowres, "cost_lowres");
+    TORCH_CHECK(cost_lowres.dim() == 4, "upsample_softargmin_var: cost must be [B,Dl,Hl,Wl]");
+    const auto c = cost_lowres.contiguous();
+    auto out = at::empty({c.size(0), h, w}, c.options()), var = at::empty_like(out);
+    OSA_CALL(osa_upsample_softargmin_var_f32(fp(c), out.data_ptr<float>(), var.data_ptr<float>(), (int)c.size(0), (int)c.size(1), (int)c.size(2), (int)c.size(3),
+                                             (int)maxdisp, (int)h, (int)w, align_corners ? 1 : 0, cur_stream()));
+    return {out, var};
+}
+
 at::Tensor context_upsample(const at::Tensor& disp_low, const at::Tensor& weights, int64_t scale, bool softmax_weights, double gain) {
     gpu_f32(disp_low, "disp_low"); gpu_f32(weights, "up_weights");
     TORCH_CHECK(disp_low.dim() == 4 && disp_low.size(1) == 1 && weights.dim() == 4 && weights.size(1) == 9, "context_upsample: disp [B,1,h,w], weights [B,9,s*h,s*w]");
@@ -229,6 +261,41 @@ at::Tensor upsample_softargmin_bwd(const at::Tensor& cost_lowres, const at::Tens
     auto ws = at::empty({(int64_t)((need + 3) / 4)}, c.options());
     OSA_CALL(osa_upsample_softargmin_bwd_ws_f32(fp(c), fp(g), dc.data_ptr<float>(), (int)c.size(0), (int)c.size(1), (int)c.size(2), (int)c.size(3), (int)maxdisp,
                                                 (int)h, (int)w, align_corners ? 1 : 0, ws.data_ptr<float>(), need, cur_stream()));
+    return dc;
+}
+
+std::tuple<at::Tensor, at::Tensor> softargmin_var_bwd(const at::Tensor& prob, const at::Tensor& disparity, const at::Tensor& dout, const at::Tensor& dvar) {
+    gpu_f32(prob, "prob"); gpu_f32(disparity, "disparity"); gpu_f32(dout, "dout"); gpu_f32(dvar, "dvar");
+    TORCH_CHECK(prob.dim() == 4 && dout.dim() == 3 && dvar.sizes() == dout.sizes(), "softargmin_var_bwd: prob [B,D,H,W], dout / dvar [B,H,W]");
+    const auto p = prob.contiguous(), d = disparity.contiguous(), g = dout.contiguous(), gv = dvar.contiguous();
+    TORCH_CHECK(d.numel() == g.numel() && g.size(0) == p.size(0) && g.size(1) == p.size(2) && g.size(2) == p.size(3), "softargmin_var_bwd: shapes disagree");
+    auto dp = at::empty_like(p), dd = at::empty(d.sizes(), d.options());
+    OSA_CALL(osa_softargmin_var_bwd_f32(fp(p), fp(d), fp(g), fp(gv), dp.data_ptr<float>(), dd.data_ptr<float>(), (int)p.size(0), (int)p.size(1), (int)p.size(2),
+                                        (int)p.size(3), cur_stream()));
+    return {dp, dd};
+}
+
+at::Tensor softmax_softargmin_var_bwd(const at::Tensor& cost, const at::Tensor& dout, const at::Tensor& dvar) {
+    gpu_f32(cost, "cost"); gpu_f32(dout, "dout"); gpu_f32(dvar, "dvar");
+    TORCH_CHECK(cost.dim() == 4 && dout.dim() == 3 && dvar.sizes() == dout.sizes(), "softmax_softargmin_var_bwd: cost [B,D,H,W], dout / dvar [B,H,W]");
+    const auto c = cost.contiguous(), g = dout.contiguous(), gv = dvar.contiguous();
+    TORCH_CHECK(g.size(0) == c.size(0) && g.size(1) == c.size(2) && g.size(2) == c.size(3), "softmax_softargmin_var_bwd: shapes disagree");
+    auto dc = at::empty_like(c);
+    OSA_CALL(osa_softmax_softargmin_var_bwd_f32(fp(c), fp(g), fp(gv), dc.data_ptr<float>(), (int)c.size(0), (int)c.size(1), (int)c.size(2), (int)c.size(3), cur_stream()));
+    return dc;
+}
+
+at::Tensor upsample_softargmin_var_bwd(const at::Tensor& cost_lowres, const at::Tensor& dout, const at::Tensor& dvar, int64_t maxdisp, int64_t h, int64_t w,
+                                       bool align_corners) {
+    gpu_f32(cost_lowres, "cost_lowres"); gpu_f32(dout, "dout"); gpu_f32(dvar, "dvar");
+    TORCH_CHECK(cost_lowres.dim() == 4 && dout.dim() == 3 && dvar.sizes() == dout.sizes(), "upsample_softargmin_var_bwd: cost [B,Dl,Hl,Wl], dout / dvar [B,h,w]");
+    const auto c = cost_lowres.contiguous(), g = dout.contiguous(), gv = dvar.contiguous();
+    TORCH_CHECK(g.size(0) == c.size(0) && g.size(1) == h && g.size(2) == w, "upsample_softargmin_var_bwd: shapes disagree");
+    auto dc = at::empty_like(c);
+    const size_t need = osa_upsample_softargmin_bwd_workspace_bytes((int)c.size(0), (int)c.size(1), (int)h, (int)w);
+    auto ws = at::empty({(int64_t)((need + 3) / 4)}, c.options());
+    OSA_CALL(osa_upsample_softargmin_var_bwd_ws_f32(fp(c), fp(g), fp(gv), dc.data_ptr<float>(), (int)c.size(0), (int)c.size(1), (int)c.size(2), (int)c.size(3),
+                                                    (int)maxdisp, (int)h, (int)w, align_corners ? 1 : 0, ws.data_ptr<float>(), need, cur_stream()));
     return dc;
 }
 
@@ -784,6 +851,25 @@ std::tuple<at::Tensor, at::Tensor> volume_bwd_meta(const at::Tensor& dvol, const
 at::Tensor softargmin_bwd_meta(const at::Tensor& g, int64_t D) { return at::empty({g.size(0), D, g.size(1), g.size(2)}, g.options()); }
 at::Tensor softmax_softargmin_bwd_meta(const at::Tensor& c, const at::Tensor&) { return at::empty_like(c); }
 at::Tensor upsample_softargmin_bwd_meta(const at::Tensor& c, const at::Tensor&, int64_t, int64_t, int64_t, bool) { return at::empty_like(c); }
+std::tuple<at::Tensor, at::Tensor> softargmin_var_meta(const at::Tensor& p, const at::Tensor& d) {
+    TORCH_CHECK(p.dim() == 4 && d.numel() == p.size(0) * p.size(2) * p.size(3), "softargmin_var: prob [B,D,H,W], disparity [B,1,H,W] or [B,H,W]");
+    return {at::empty({p.size(0), p.size(2), p.size(3)}, p.options()), at::empty({p.size(0), p.size(2), p.size(3)}, p.options())};
+}
+std::tuple<at::Tensor, at::Tensor> softmax_softargmin_var_meta(const at::Tensor& c) {
+    TORCH_CHECK(c.dim() == 4, "softmax_softargmin_var: [B,D,H,W]");
+    return {at::empty({c.size(0), c.size(2), c.size(3)}, c.options()), at::empty({c.size(0), c.size(2), c.size(3)}, c.options())};
+}
+std::tuple<at::Tensor, at::Tensor> upsample_softargmin_var_meta(const at::Tensor& c, int64_t, int64_t h, int64_t w, bool) {
+    TORCH_CHECK(c.dim() == 4, "upsample_softargmin_var: [B,Dl,Hl,Wl]");
+    return {at::empty({c.size(0), h, w}, c.options()), at::empty({c.size(0), h, w}, c.options())};
+}
+std::tuple<at::Tensor, at::Tensor> softargmin_var_bwd_meta(const at::Tensor& p, const at::Tensor& d, const at::Tensor&, const at::Tensor&) {
+    return {at::empty(p.sizes(), p.options()), at::empty(d.sizes(), d.options())};
+}
+at::Tensor softmax_softargmin_var_bwd_meta(const at::Tensor& c, const at::Tensor&, const at::Tensor&) { return at::empty(c.sizes(), c.options()); }
+at::Tensor upsample_softargmin_var_bwd_meta(const at::Tensor& c, const at::Tensor&, const at::Tensor&, int64_t, int64_t, int64_t, bool) {
+    return at::empty(c.sizes(), c.options());
+}
 
 // ---- autograd in C++ (TORCH_LIBRARY_IMPL(osa_native, Autograd, ...)): torch.ops.osa_native.* are differentiable without any Python ------
 // Each Function redispatches below the Autograd key for its forward and calls the *_bwd op in backward (so double tracing sees ops, too).
@@ -897,6 +983,73 @@ struct UpsampleSoftargminFn : torch::autograd::Function<UpsampleSoftargminFn> {
 };
 at::Tensor upsample_softargmin_autograd(const at::Tensor& c, int64_t maxdisp, int64_t h, int64_t w, bool align) { return UpsampleSoftargminFn::apply(c, maxdisp, h, w, align); }
 
+// disparity + variance heads: two differentiable results each (an unused one arrives as a zero gradient: Function materialises grads)
+using tensor_pair = std::tuple<at::Tensor, at::Tensor>;
+struct SoftargminVarFn : torch::autograd::Function<SoftargminVarFn> {
+    static variable_list forward(AutogradContext* ctx, const at::Tensor& p, const at::Tensor& d) {
+        at::AutoDispatchBelowADInplaceOrView g;
+        ctx->save_for_backward({p, d});
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("osa_native::softargmin_var", "").typed<tensor_pair(const at::Tensor&, const at::Tensor&)>();
+        auto [out, var] = op.call(p, d);
+        return {out, var};
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list gy) {
+        const auto sv = ctx->get_saved_variables();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("osa_native::softargmin_var_bwd", "")
+            .typed<tensor_pair(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&)>();
+        auto [dp, dd] = op.call(sv[0].to(at::kFloat), sv[1].to(at::kFloat), gy[0].to(at::kFloat), gy[1].to(at::kFloat));
+        return {dp.to(sv[0].scalar_type()), dd.to(sv[1].scalar_type())};
+    }
+};
+tensor_pair softargmin_var_autograd(const at::Tensor& p, const at::Tensor& d) {
+    auto r = SoftargminVarFn::apply(p, d);
+    return {r[0], r[1]};
+}
+
+struct SoftmaxSoftargminVarFn : torch::autograd::Function<SoftmaxSoftargminVarFn> {
+    static variable_list forward(AutogradContext* ctx, const at::Tensor& c) {
+        at::AutoDispatchBelowADInplaceOrView g;
+        ctx->save_for_backward({c});
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("osa_native::softmax_softargmin_var", "").typed<tensor_pair(const at::Tensor&)>();
+        auto [out, var] = op.call(c);
+        return {out, var};
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list gy) {
+        const auto c = ctx->get_saved_variables()[0];
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("osa_native::softmax_softargmin_var_bwd", "")
+            .typed<at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&)>();
+        return {op.call(c.to(at::kFloat), gy[0].to(at::kFloat), gy[1].to(at::kFloat)).to(c.scalar_type())};
+    }
+};
+tensor_pair softmax_softargmin_var_autograd(const at::Tensor& c) {
+    auto r = SoftmaxSoftargminVarFn::apply(c);
+    return {r[0], r[1]};
+}
+
+struct UpsampleSoftargminVarFn : torch::autograd::Function<UpsampleSoftargminVarFn> {
+    static variable_list forward(AutogradContext* ctx, const at::Tensor& c, int64_t maxdisp, int64_t h, int64_t w, bool align) {
+        at::AutoDispatchBelowADInplaceOrView g;
+        ctx->save_for_backward({c});
+        ctx->saved_data["maxdisp"] = maxdisp; ctx->saved_data["h"] = h; ctx->saved_data["w"] = w; ctx->saved_data["align"] = align;
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("osa_native::upsample_softargmin_var", "")
+            .typed<tensor_pair(const at::Tensor&, int64_t, int64_t, int64_t, bool)>();
+        auto [out, var] = op.call(c, maxdisp, h, w, align);
+        return {out, var};
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list gy) {
+        const auto c = ctx->get_saved_variables()[0];
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("osa_native::upsample_softargmin_var_bwd", "")
+            .typed<at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t, int64_t, bool)>();
+        auto dc = op.call(c.to(at::kFloat), gy[0].to(at::kFloat), gy[1].to(at::kFloat), ctx->saved_data["maxdisp"].toInt(), ctx->saved_data["h"].toInt(),
+                          ctx->saved_data["w"].toInt(), ctx->saved_data["align"].toBool());
+        return {dc.to(c.scalar_type()), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+tensor_pair upsample_softargmin_var_autograd(const at::Tensor& c, int64_t maxdisp, int64_t h, int64_t w, bool align) {
+    auto r = UpsampleSoftargminVarFn::apply(c, maxdisp, h, w, align);
+    return {r[0], r[1]};
+}
+
 int64_t abi_version() { return osa_abi_version(); }
 
 // ---- Meta (FakeTensor / torch.export / torch.compile) kernels of the launch ops (r6) ------------------------------------------------------
@@ -964,6 +1117,13 @@ TORCH_LIBRARY(osa_native, m) {
     m.def("softargmin_bwd(Tensor dout, int D) -> Tensor");
     m.def("softmax_softargmin_bwd(Tensor cost, Tensor dout) -> Tensor");
     m.def("upsample_softargmin_bwd(Tensor cost_lowres, Tensor dout, int maxdisp, int h, int w, bool align_corners=False) -> Tensor");
+    // disparity + variance heads (-> (disp, var), [B,H,W] each) and their backward ops
+    m.def("softargmin_var(Tensor prob, Tensor disparity) -> (Tensor, Tensor)");
+    m.def("softmax_softargmin_var(Tensor cost) -> (Tensor, Tensor)");
+    m.def("upsample_softargmin_var(Tensor cost_lowres, int maxdisp, int h, int w, bool align_corners=False) -> (Tensor, Tensor)");
+    m.def("softargmin_var_bwd(Tensor prob, Tensor disparity, Tensor dout, Tensor dvar) -> (Tensor, Tensor)");
+    m.def("softmax_softargmin_var_bwd(Tensor cost, Tensor dout, Tensor dvar) -> Tensor");
+    m.def("upsample_softargmin_var_bwd(Tensor cost_lowres, Tensor dout, Tensor dvar, int maxdisp, int h, int w, bool align_corners=False) -> Tensor");
     m.def("cost_volume_cl(Tensor gwc_feat, Tensor? cat_feat, int B, int num_groups, int maxdisp, int gwc_channels, int cat_channels, int gwc_off, bool mask_left, "
           "bool out_split, Tensor? gwc_meta, Tensor? cat_meta, Tensor(a!) out_meta) -> (Tensor, bool)");
     m.def("conv_wgrad(Tensor x, Tensor dy, Tensor(a!) dw, int[] dims, int prec, Tensor? x_meta, Tensor? dy_meta) -> bool");
@@ -1020,6 +1180,12 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
     m.impl("softargmin_bwd", &softargmin_bwd);
     m.impl("softmax_softargmin_bwd", &softmax_softargmin_bwd);
     m.impl("upsample_softargmin_bwd", &upsample_softargmin_bwd);
+    m.impl("softargmin_var", &softargmin_var);
+    m.impl("softmax_softargmin_var", &softmax_softargmin_var);
+    m.impl("upsample_softargmin_var", &upsample_softargmin_var);
+    m.impl("softargmin_var_bwd", &softargmin_var_bwd);
+    m.impl("softmax_softargmin_var_bwd", &softmax_softargmin_var_bwd);
+    m.impl("upsample_softargmin_var_bwd", &upsample_softargmin_var_bwd);
     m.impl("cost_volume_cl", &cost_volume_cl);
     m.impl("conv_wgrad", &conv_wgrad);
     m.impl("conv_wgrad_multi", &conv_wgrad_multi);
@@ -1071,6 +1237,12 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
     m.impl("softargmin_bwd", &softargmin_bwd_meta);
     m.impl("softmax_softargmin_bwd", &softmax_softargmin_bwd_meta);
     m.impl("upsample_softargmin_bwd", &upsample_softargmin_bwd_meta);
+    m.impl("softargmin_var", &softargmin_var_meta);
+    m.impl("softmax_softargmin_var", &softmax_softargmin_var_meta);
+    m.impl("upsample_softargmin_var", &upsample_softargmin_var_meta);
+    m.impl("softargmin_var_bwd", &softargmin_var_bwd_meta);
+    m.impl("softmax_softargmin_var_bwd", &softmax_softargmin_var_bwd_meta);
+    m.impl("upsample_softargmin_var_bwd", &upsample_softargmin_var_bwd_meta);
     // r6: every launch op -- an engine model traces under FakeTensorMode / make_fx without a kernel running (tests/test_gpu_fake_trace.py)
     m.impl("cost_volume_cl", &cost_volume_cl_meta);
     m.impl("conv_wgrad", &conv_wgrad_meta);
@@ -1094,4 +1266,7 @@ TORCH_LIBRARY_IMPL(osa_native, Autograd, m) {    // differentiable in C++: backw
     m.impl("softargmin", &softargmin_autograd);
     m.impl("softmax_softargmin", &softmax_softargmin_autograd);
     m.impl("upsample_softargmin", &upsample_softargmin_autograd);
+    m.impl("softargmin_var", &softargmin_var_autograd);
+    m.impl("softmax_softargmin_var", &softmax_softargmin_var_autograd);
+    m.impl("upsample_softargmin_var", &upsample_softargmin_var_autograd);
 }

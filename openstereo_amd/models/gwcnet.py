@@ -364,7 +364,7 @@ class GwcDispProcessor(nn.Module):
             preds.append(AG.upsample_softargmin(cost, self.maxdisp, h, w, align_corners=False))
         return {"training_disp": {"disp": {"disp_ests": preds}}}
 
-    def forward(self, inputs):
+    def forward(self, inputs, return_variance=False):
         if self.training:
             return self.forward_train(inputs)
         volume = inputs["cost_volume"]
@@ -372,6 +372,9 @@ class GwcDispProcessor(nn.Module):
         if not ops.is_cl(volume) or volume.shape[1] % 4:
             volume = ops.to_cl(volume)
         cost3 = self.aggregate_cl(volume)
+        if return_variance:                                              # opt-in (GwcNet.return_variance): the same head kernel with a second result
+            pred3, var3 = ops.upsample_softargmin(cost3, self.maxdisp, h, w, align_corners=False, return_variance=True)
+            return {"inference_disp": {"disp_est": pred3, "disp_var": var3}}
         pred3 = ops.upsample_softargmin(cost3, self.maxdisp, h, w, align_corners=False)
         return {"inference_disp": {"disp_est": pred3}}
 
@@ -389,7 +392,12 @@ GWCNET_G_SCENEFLOW = _Cfg(MAX_DISP=192, USE_CONCAT_VOLUME=True, CONCAT_CHANNELS=
 
 
 class GwcNet(nn.Module):
-    """models/gwcnet/gwcnet.py:11-39: forward(dict{'left','right'}) -> {'disp_pred': [B,H,W]}."""
+    """models/gwcnet/gwcnet.py:11-39: forward(dict{'left','right'}) -> {'disp_pred': [B,H,W]}.
+    `model.return_variance = True` (opt-in, eval mode): the dict also holds 'disp_var' [B,H,W], the per-pixel variance of the disparity
+    distribution the final head regresses from (reference: disparity_variance, cfnet/submodule.py:128-134), from the same kernel pass;
+    'disp_pred' keeps its bits.  Read with getattr: the reference's own GwcNet class, grafted with this forward, has no such attribute."""
+
+    return_variance = False
 
     def __init__(self, cfgs=GWCNET_G_SCENEFLOW):
         super().__init__()
@@ -427,11 +435,17 @@ class GwcNet(nn.Module):
                 # absent in this mode (OSA_VOL_SPLIT=0 or the exact-f32 mode publish the fp32 NDHWC volume).
                 dp = self.DispProcessor
                 h, w = inputs["left"].shape[2:]
+                if getattr(self, "return_variance", False):
+                    pred, var = ops.upsample_softargmin(dp.aggregate_cl(vol), dp.maxdisp, h, w, align_corners=False, return_variance=True)
+                    return {"disp_pred": pred, "disp_var": var}
                 return {"disp_pred": ops.upsample_softargmin(dp.aggregate_cl(vol), dp.maxdisp, h, w, align_corners=False)}
             inputs["cost_volume"] = vol
         else:
             inputs.update(self.Backbone(inputs))
             inputs.update(self.CostProcessor(inputs))
+        if not self.training and getattr(self, "return_variance", False):
+            est = self.DispProcessor(inputs, return_variance=True)["inference_disp"]
+            return {"disp_pred": est["disp_est"], "disp_var": est["disp_var"]}
         disp_out = self.DispProcessor(inputs)
         if self.training:
             ests = disp_out["training_disp"]["disp"]["disp_ests"]

@@ -320,18 +320,27 @@ class PSMDispProcessor(nn.Module):
         self.max_disp = max_disp
         self.disp_processor = ops.FasterSoftArgmin(max_disp=max_disp, start_disp=0, dilation=1, alpha=1.0, normalize=True)
 
-    def forward(self, inputs):
+    def forward(self, inputs, return_variance=False):
+        """return_variance=True (PSMNet.return_variance): -> (disparities, variance of the final cost's distribution [B,h,w]); the fused
+        head gives both maps in one kernel pass, its disparity holding the bits of the call without the variance."""
         h, w = inputs["left"].shape[2:]
-        out = []
+        D = self.disp_processor.max_disp
+        out, var = [], None
+        if return_variance and inputs["cost3"].dim() != 5:      # the reference's full-resolution cost goes through FasterSoftArgmin, which has no variance
+            raise ops._lib.EngineError("return_variance needs the engine's low-res cost3 [B,1,D/4,H/4,W/4], not a full-resolution [B,D,H,W] cost")
         for k in ("cost1", "cost2", "cost3"):
             c = inputs[k]
+            rv = return_variance and k == "cost3"
             if c.dim() == 5 and torch.is_grad_enabled() and c.requires_grad:      # training: fused head with its backward kernel
-                out.append(AG.upsample_softargmin(c, self.disp_processor.max_disp, h, w, align_corners=True))
+                d = AG.upsample_softargmin_variance(c, D, h, w, align_corners=True) if rv else AG.upsample_softargmin(c, D, h, w, align_corners=True)
             elif c.dim() == 5:
-                out.append(ops.upsample_softargmin(c, self.disp_processor.max_disp, h, w, align_corners=True))
+                d = ops.upsample_softargmin(c, D, h, w, align_corners=True, **({"return_variance": True} if rv else {}))   # off: today's call
             else:
-                out.append(self.disp_processor(c))
-        return out
+                d = self.disp_processor(c)
+            if rv:
+                d, var = d
+            out.append(d)
+        return (out, var) if return_variance else out
 
 
 class _Cfg(dict):
@@ -348,9 +357,14 @@ class PSMNet(nn.Module):
         self.CostProcessor = PSMCostProcessor(max_disp=self.maxdisp)
         self.DispProcessor = PSMDispProcessor(max_disp=self.maxdisp)
 
+    return_variance = False     # opt-in, eval mode: adds 'disp_var' [B,H,W], the variance of the final cost's disparity distribution
+
     def forward(self, inputs):
         inputs.update(self.Backbone(inputs))
         inputs.update(self.CostProcessor(inputs))
+        if getattr(self, "return_variance", False) and not self.training:       # getattr: the reference's own class, grafted with this forward, has no such attribute
+            disp_out, var = self.DispProcessor(inputs, return_variance=True)
+            return {"disp_pred": disp_out[-1], "train_preds": disp_out, "disp_var": var}
         disp_out = self.DispProcessor(inputs)
         return {"disp_pred": disp_out[-1], "train_preds": disp_out}
 

@@ -13,8 +13,10 @@ Reference                                                      here
   disp_pred.disparity_regression (keepdim=True)                disparity_regression
   gwcnet_disp_processor.disparity_regression (keepdim=False)   disparity_regression(..., keepdim=False)
   psmnet_disp_processor.FasterSoftArgmin                       FasterSoftArgmin
+  cfnet / igevpp submodule.disparity_variance(x,maxdisp,disp)  disparity_variance
 Engine-only fused entry points (no reference equivalent, they replace op chains):
   build_cost_volume_cl, softmax_disparity_regression, upsample_softargmin
+  (the last two with return_variance=True: the per-pixel variance of the distribution beside the disparity)
 """
 from __future__ import annotations
 
@@ -267,21 +269,41 @@ def disparity_regression(x, maxdisp, keepdim=True):
     return out.unsqueeze(1) if keepdim else out
 
 
-def softmax_disparity_regression(cost, maxdisp=None, keepdim=True, return_prob=False):
-    """F.softmax(cost, dim=1) + disparity_regression in one kernel (stereobase_gru.py:163-164)."""
+def disparity_variance(x, maxdisp, disparity):
+    """cfnet/submodule.py:128-134 == igevpp/submodule.py:153-159: sum_d x[:,d] * (d - disparity)^2 -> [B,1,H,W].  `x` [B,maxdisp,H,W] need
+    not be normalised, `disparity` [B,1,H,W] need not be its mean.  fp32 inside an autocast region, like disparity_regression."""
+    assert len(x.shape) == 4                                      # submodule.py:130
+    _chk(x, "x"); _chk(disparity, "disparity")
+    B, D, H, W = x.shape
+    assert D == maxdisp, f"x has {D} disparity planes, maxdisp={maxdisp}"
+    assert disparity.numel() == B * H * W, f"disparity must be [B,1,H,W], got {tuple(disparity.shape)}"
+    _, var = _ext.load().softargmin_var(_f32c(x), _f32c(disparity))
+    od = _sum_dtype(x, disparity)
+    return (var if od == torch.float32 else var.to(od)).unsqueeze(1)
+
+
+def softmax_disparity_regression(cost, maxdisp=None, keepdim=True, return_prob=False, return_variance=False):
+    """F.softmax(cost, dim=1) + disparity_regression in one kernel (stereobase_gru.py:163-164).
+    return_variance=True: -> (disp, var), var = sum_d p_d (d - disp)^2 in disp's shape (fp32), from one kernel."""
     assert len(cost.shape) == 4
     _chk(cost, "cost")
     if maxdisp is not None:
         assert cost.shape[1] == maxdisp
+    if return_variance:
+        assert not return_prob, "return_variance and return_prob are separate kernels: ask for one"
+        out, var = _ext.load().softmax_softargmin_var(_f32c(cost))
+        return (out.unsqueeze(1), var.unsqueeze(1)) if keepdim else (out, var)
     out, prob = _ext.load().softmax_softargmin(_f32c(cost), bool(return_prob))
     out = out.unsqueeze(1) if keepdim else out
     return (out, prob) if return_prob else out
 
 
-def upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners=False):
+def upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners=False, return_variance=False):
     """F.interpolate(cost[:,None], [maxdisp,h,w], 'trilinear') -> squeeze -> softmax(dim=1) ->
     disparity_regression(keepdim=False), fused (gwcnet_disp_processor.py:128-133; PSMNet uses
-    align_corners=True, psmnet_cost_processor.py:201-214).  cost_lowres: [B,Dl,Hl,Wl] or [B,1,Dl,Hl,Wl]."""
+    align_corners=True, psmnet_cost_processor.py:201-214).  cost_lowres: [B,Dl,Hl,Wl] or [B,1,Dl,Hl,Wl].
+    return_variance=True: -> (disp, var), both fp32 [B,h,w]; var is disparity_variance of the same (never materialised) probabilities
+    about disp, and disp holds the bits the call without the flag returns."""
     _chk(cost_lowres, "cost_lowres")
     if cost_lowres.dim() == 5:
         assert cost_lowres.shape[1] == 1
@@ -289,6 +311,9 @@ def upsample_softargmin(cost_lowres, maxdisp, h, w, align_corners=False):
     assert cost_lowres.dim() == 4
     cs = _f32c(cost_lowres)
     _, Dl, Hl, Wl = cs.shape
+    if return_variance:
+        with timing.span("upsample_softargmin_var", Dl, Hl, Wl, int(maxdisp), int(h), int(w)):
+            return _ext.load().upsample_softargmin_var(cs, int(maxdisp), int(h), int(w), bool(align_corners))
     with timing.span("upsample_softargmin", Dl, Hl, Wl, int(maxdisp), int(h), int(w)):
         return _ext.load().upsample_softargmin(cs, int(maxdisp), int(h), int(w), bool(align_corners))
 
