@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 8
+#define OSA_ABI_VERSION 9
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -686,6 +686,23 @@ long long osa_conv3d_march_launches(void);
  * parity-planar LDS image.  Same arguments, same semantics; results agree with the brick form to fp32 rounding.  Bit 29 of
  * osa_conv_b_ring_mask switches the form (A/B runs, parity tests); this counter tells how many calls took it. */
 long long osa_conv3d_march_s2_launches(void);
+
+/* ---- output-plane-walking form of the fused stride-2 transposed convolutions (r7, csrc/conv_deconv_walk.h) ----
+ * osa_deconv3d_redir_ndhwc_f16x3 runs eligible layers as workgroups that own a tile of input pixels and walk a segment of OUTPUT planes: an
+ * even plane takes its 9 taps from one input plane, an odd plane 18 taps from two; only the four (h, w) parity classes of one plane are
+ * live.  Eligible: 3-D, k = 3 / p = 1 / op = 1, split input, redir input and output, Ci % 16 == 0, and Co == redir channels == 32 (conv6 +
+ * redir1 of the GwcNet hourglasses, 64 -> 32 -- models/gwcnet/hourglass.py:36-56) or == 64 (conv5 + redir2, 128 -> 64), channel strides
+ * multiples of 16, activation none / relu / leaky, no residual or gate.  Same arguments, same semantics, the same scale published for the
+ * next layer; results agree with the brick form to fp32 rounding (different summation order).  Everything else (f32 / f16 modes, 2-D,
+ * k = 4, residual or gate, fp32 tensors, other channel counts) keeps the brick kernel.
+ * osa_deconv_walk(enable): bit 0 = the 32-output-channel class, bit 1 = the 64-output-channel class (0: brick form for both).  Returns
+ * the previous value.  It exists for A/B measurements and for the parity test against the brick form.
+ * osa_deconv_walk_segment_planes(planes): debug setter -- output planes a workgroup walks (0, the shipped state: the launcher's cost
+ * model); for the segment-length ablation and for tests on shapes the cost model would cut into one-plane segments.  Returns the previous value.
+ * osa_deconv3d_walk_launches: calls of this process that took the walking form. */
+int osa_deconv_walk(int enable);
+int osa_deconv_walk_segment_planes(int planes);
+long long osa_deconv3d_walk_launches(void);
 
 /* ---- B (weight) operands through an LDS ring (r4, csrc/conv_kernel.h BL = 1; f16x3 and f16 modes) ----
  * Every convolution / transposed convolution entry point above (the MFMA tiles behind nn.Conv3d / nn.Conv2d / nn.ConvTranspose3d of

@@ -200,6 +200,9 @@ SIGNATURES = {
     "osa_channel_sums": (c_i, [c_fp, c_i, c_i, c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_ll, c_i, c_fp, c_fp, C.c_size_t, c_st]),
     "osa_conv3d_march_launches": (c_ll, []),
     "osa_conv3d_march_s2_launches": (c_ll, []),
+    "osa_deconv_walk": (c_i, [c_i]),
+    "osa_deconv_walk_segment_planes": (c_i, [c_i]),
+    "osa_deconv3d_walk_launches": (c_ll, []),
     "osa_conv_b_ring_mask": (c_i, [c_i]),
     "osa_conv_b_ring_launches": (c_ll, []),
     "osa_volume_walk_step": (c_i, [c_i]),
@@ -244,6 +247,8 @@ def load():
             raise EngineError(f"ABI version mismatch: library reports {lib.osa_abi_version()}, include/openstereo_amd.h declares {abi_version(lib)}")
         if os.environ.get("OSA_B_RING_MASK"):
             lib.osa_conv_b_ring_mask(int(os.environ["OSA_B_RING_MASK"], 0))     # A/B runs: which tiles take their weights through the LDS ring
+        if os.environ.get("OSA_DECONV_WALK"):
+            lib.osa_deconv_walk(int(os.environ["OSA_DECONV_WALK"], 0))        # A/B runs: which fused transposed layer classes take the walking form
         if os.environ.get("OSA_VOL_WALK"):
             lib.osa_volume_walk_step(int(os.environ["OSA_VOL_WALK"]))               # A/B runs: 0 = chunked volume builder, 4 / 8 = d-walking form
         _lib = lib

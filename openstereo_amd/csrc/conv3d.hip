@@ -232,6 +232,8 @@ int launch_conv_march(ConvArgs& a, hipStream_t st, const char* what);
 // d-marching form of the 3x3x3 stride-2 64-output-channel layers (f16x3, split tensors): conv_march.hip / conv_march_s2.h.  Switch: bit 29 of
 // osa_conv_b_ring_mask (A/B runs and the parity test against the brick form)
 int launch_conv_march_s2(ConvArgs& a, hipStream_t st, const char* what);
+// output-plane-walking form of the fused transposed convolutions (conv_deconv_walk.h, launched from conv_march.hip; osa_deconv_walk switches it)
+int launch_conv_deconv_walk(ConvArgs& a, hipStream_t st, const char* what);
 void wgrad_set_multi_tile(int on);   // bit 27 of the mask: the multi-tile form of the f16x3 / f16 weight gradient (csrc/wgrad.hip wgrad_mt_kernel); 0 = single-tile kernel
 void march_s2_set_waves(int w);     // bit 28 of the mask: the 4-wave 2 x 32 column (two workgroups per CU) instead of the 8-wave 4 x 32 column (one per CU)
 
@@ -996,6 +998,10 @@ static int deconv3d_impl(const float* x, const float* w_packed,
     }
     set_ranges(a, rng);
     if (check_split_ranges(a, prec, flat ? "deconv2d" : "deconv3d")) return -1;
+    if (prec == PREC_F16X3 && !flat && k == 3 && rx) {
+        const int r = launch_conv_deconv_walk(a, (hipStream_t)stream, "deconv3d (walk)");
+        if (r != 0) return r < 0 ? r : 0;
+    }
     return launch_conv(a, 1, prec, (hipStream_t)stream, flat ? "deconv2d" : "deconv3d",
                        flat ? &g_deconv_flat_cfg : (rx ? (rCi > 32 ? &g_deconv_redir64_cfg : &g_deconv_redir_cfg) : &g_deconv_cfg));
 }

@@ -277,6 +277,18 @@ __device__ __forceinline__ void wait_vmcnt(const int n) {
     }
 }
 
+// One LDS-DMA instruction: 64 x 16 bytes, lane i -> LDS [lds_byte + 16 i] (wave-uniform base through M0) from a per-lane global address.
+// Inline asm on purpose (conv_march.h): through the builtin the compiler orders every later ds_read behind the transfer.  Nothing orders a
+// read behind it but the issuing wave's vmcnt wait (+ a barrier for the other waves); every wave issues every instruction with all lanes
+// on -- lanes without data fetch from g_lds_dma_zeros -- so that the vmcnt immediates of the protocols count instructions.
+__device__ const float4 g_lds_dma_zeros[4] = {};
+__device__ __forceinline__ void lds_dma16(const char* src, const unsigned lds_byte) {
+    const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_byte);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(src), "s"(m0v) : "memory");
+}
+
 // In-kernel timeline (build with -DOSA_EXPERIMENTS -DOSA_TRACE_ON, run with OSA_DBG & 256): wave `w` of every 97th workgroup stamps the 100 MHz wall clock at its
 // phase boundaries into g_trace[slot][wave][event]; tools/trace_conv.py reads it back (osa_debug_trace_read).
 #ifdef OSA_TRACE_ON

@@ -48,8 +48,6 @@ struct MarchGeo {
     static_assert(NP <= 7, "one piece per wave and step, all of them forced home by the waits of steps 2..8");
 };
 
-__device__ const float4 g_march_zeros[4] = {};       // source of the LDS-DMA lanes that fill padding / out-of-image slots
-
 // INS = 1: the input is a split tensor (16-byte quads are the LDS image: asynchronous LDS-DMA staging); INS = 0: fp32 input, split while
 // it is staged through registers at the start of every pass (GwcNet: dres0.0 only, which reads the volume builder's fp32 output).
 template <int NWV, int TW, int OUTS, int INS>
@@ -121,15 +119,10 @@ __global__ __launch_bounds__(NWV * 64, 2) void conv_march_kernel(const ConvArgs 
     // which is exactly the wait the rings exist to avoid; the hardware orders nothing (MI355X_MICROARCH.md), the vmcnt / barrier protocol
     // below does.  Every instruction is issued by every wave with all lanes on (lanes without data fetch zeros): the vmcnt immediates
     // of the protocol count instructions.
-    auto dma = [&](const char* src, const unsigned lds_byte) {
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_byte);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(m0v) : "memory");
-    };
+    auto dma = [&](const char* src, const unsigned lds_byte) { lds_dma16(src, lds_byte); };
     const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     const unsigned bring_lds = smem_lds + 2u * PLANEQ * 16u;
-    const char* const zsrc = reinterpret_cast<const char*>(g_march_zeros);
+    const char* const zsrc = reinterpret_cast<const char*>(g_lds_dma_zeros);
 
     // B: a step's 6 KB = 384 float4 slots [fragment f = kd * 2 + hl][64 lanes], split evenly over the waves: wave w fetches slots
     // [w * 96, (w + 1) * 96) with NI = 2 instructions (the second covers 32 slots: its upper lanes are switched off by the exec mask,

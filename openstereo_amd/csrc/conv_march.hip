@@ -2,6 +2,7 @@
 // brick kernel's ~200 instantiations (conv3d.hip) are not recompiled with it.
 #include "conv_march.h"
 #include "conv_march_s2.h"
+#include "conv_deconv_walk.h"
 
 namespace osa {
 
@@ -145,7 +146,82 @@ int launch_conv_march_s2(ConvArgs& a, hipStream_t st, const char* what) {
     return r;
 }
 
+// ------------------------------------------------------------------ output-plane-walking transposed form (conv_deconv_walk.h) --
+// 3-D stride-2 transposed convolutions k = 3 / p = 1 / op = 1 with the fused redir branch, f16x3 mode, split input, redir input and output,
+// 32 or 64 output channels with as many redir channels (conv6 / conv5 of the GwcNet hourglasses).  Returns 1 when launched, 0 when the
+// layer is not eligible or its class is switched off (the brick kernel then runs it), -1 on error.
+static long long g_deconv_walk_launches = 0;
+long long deconv_walk_launches() { return g_deconv_walk_launches; }
+
+// osa_deconv_walk: bit 0 = the 32-output-channel class (conv6), bit 1 = the 64-output-channel class (conv5).  Defaults by measurement:
+// profiles/round7/deconv_walk.md.
+static int g_deconv_walk = 2;
+int deconv_walk_set(int enable) { const int prev = g_deconv_walk; g_deconv_walk = enable & 3; return prev; }
+// osa_deconv_walk_segment_planes: output planes per segment, 0 = the launcher's cost model (the shipped state).  A debug setter of its own, for
+// the segment-length ablation and for the tests, whose small shapes the cost model would cut into one-plane segments.
+static int g_deconv_walk_planes = 0;
+int deconv_walk_planes_set(int planes) { const int prev = g_deconv_walk_planes; g_deconv_walk_planes = planes > 0 ? planes : 0; return prev; }
+
+template <int WN, int RCH>
+static int launch_conv_deconv_walk_t(ConvArgs& a, hipStream_t st, const char* what) {
+    using G = DeconvWalkGeo<WN>;
+    a.tilesD = 1; a.tilesH = cdiv(a.Hi, G::TH); a.tilesW = cdiv(a.Wi, G::TW);
+    // stream index of tap (kd, kh, kw) in the class-major packed stream: class c = (pd, ph, pw) holds the taps of its parity; an even
+    // parity has the one tap k = 1 (delta 0), an odd parity k = 0 (delta + 1) and k = 2 (delta 0)
+    for (int t = 0, c = 0; t < a.T; ++t) {
+        while (t >= a.cls_end[c]) ++c;
+        const int kd = ((c >> 2) & 1) ? (a.td[t] == 1 ? 0 : 2) : 1;
+        const int kh = ((c >> 1) & 1) ? (a.th[t] == 1 ? 0 : 2) : 1;
+        const int kw = (c & 1) ? (a.tw[t] == 1 ? 0 : 2) : 1;
+        a.toff[kd * 9 + kh * 3 + kw] = t;
+    }
+    // segments of `oseg` output planes (an even plane is one source plane, an odd one two; no boundary planes).  Cost model in source-plane
+    // passes per round of resident workgroups (2 per CU); the fewest segments win a tie.
+    const long long cols = (long long)a.B * a.tilesH * a.tilesW;
+    const long long slots = 2 * 256;
+    int nseg = 1;
+    {
+        double best = 1e30;
+        for (int n = 1; n <= a.Do; ++n) {
+            const int os = cdiv(a.Do, n), ns = cdiv(a.Do, os);
+            if (ns != n) continue;
+            const double cost = (double)((cols * ns + slots - 1) / slots) * (1.5 * os + 0.5);     // (+ 0.5: prologue / drain of a workgroup)
+            if (cost < best - 1e-9) { best = cost; nseg = ns; }
+        }
+    }
+    int oseg = cdiv(a.Do, nseg);
+    if (g_deconv_walk_planes > 0) oseg = g_deconv_walk_planes < a.Do ? g_deconv_walk_planes : a.Do;
+    nseg = cdiv(a.Do, oseg);
+    OSA_REQUIRE(cols * nseg < (1ll << 31), "%s: grid too large", what);
+    OSA_REQUIRE(hipFuncSetAttribute((const void*)conv_deconv_walk_kernel<WN, RCH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes()) == hipSuccess,
+                "%s: %d bytes of LDS per workgroup refused", what, (int)G::lds_bytes());
+    hipLaunchKernelGGL((conv_deconv_walk_kernel<WN, RCH>), dim3((unsigned)(cols * nseg)), dim3(G::NWV * 64), G::lds_bytes(), st, a, oseg, nseg);
+    OSA_LAUNCH_CHECK(what);
+    return 1;
+}
+
+int launch_conv_deconv_walk(ConvArgs& a, hipStream_t st, const char* what) {
+    // ELIGIBILITY (argument validation has run in deconv3d_impl): anything else falls through to the brick kernel
+    if (a.T != 27 || a.Do != 2 * a.Di || a.Ho != 2 * a.Hi || a.Wo != 2 * a.Wi) return 0;          // 3-D, k = 3 / p = 1 / op = 1
+    if (!a.rx || a.res || a.gate) return 0;
+    const int cls = (a.Co == 32 && a.rCi == 32) ? 0 : ((a.Co == 64 && a.rCi == 64) ? 1 : -1);
+    if (cls < 0 || a.CoP != a.Co || !((g_deconv_walk >> cls) & 1)) return 0;
+    if (!(a.act & OSA_IN_SPLIT) || !(a.act & OSA_OUT_SPLIT) || !(a.act & OSA_REDIR_SPLIT)) return 0;
+    const int actk = a.act & 15;
+    if (actk > OSA_ACT_LEAKY || (a.act & (OSA_GATE_RAW | OSA_RES_AFTER_ACT)) || ((unsigned)a.act >> 16)) return 0;
+    if (a.Ci % 16 != 0 || a.xCs % 16 != 0 || a.yCs % 16 != 0 || a.rxCs % 16 != 0) return 0;
+    if (((size_t)a.x & 15) || ((size_t)a.y & 15) || ((size_t)a.rx & 15)) return 0;
+    if ((long long)a.Do * a.Ho * a.Wo * (a.yCs > a.rxCs ? a.yCs : a.rxCs) >= (1ll << 31)) return 0;
+    if ((long long)a.Hi * a.Wi * a.xCs >= (1ll << 29)) return 0;        // per-plane byte offsets are 32-bit
+    const int r = cls == 0 ? launch_conv_deconv_walk_t<1, 2>(a, st, what) : launch_conv_deconv_walk_t<2, 4>(a, st, what);
+    if (r == 1) ++g_deconv_walk_launches;
+    return r;
+}
+
 }  // namespace osa
 
 extern "C" long long osa_conv3d_march_launches(void) { return osa::march_launches(); }
 extern "C" long long osa_conv3d_march_s2_launches(void) { return osa::march_s2_launches(); }
+extern "C" long long osa_deconv3d_walk_launches(void) { return osa::deconv_walk_launches(); }
+extern "C" int osa_deconv_walk(int enable) { return osa::deconv_walk_set(enable); }
+extern "C" int osa_deconv_walk_segment_planes(int planes) { return osa::deconv_walk_planes_set(planes); }

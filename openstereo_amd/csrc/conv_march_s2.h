@@ -46,8 +46,6 @@ struct MarchS2Geo {
     static_assert((size_t)NWV * 32 * 36 * 4 <= (size_t)PLANEQ * 16, "epilogue tiles must fit into one plane buffer");
 };
 
-__device__ const float4 g_march_s2_zeros[4] = {};
-
 template <int N>
 __device__ __forceinline__ void wait_vmcnt_c() {
     static_assert(N >= 0 && N <= 15, "vmcnt immediate");
@@ -108,15 +106,10 @@ __global__ __launch_bounds__(NWV_ * 64, 2) void conv_march_s2_kernel(const ConvA
     float* const yb = p.y + (size_t)b * p.Do * p.Ho * p.Wo * p.yCs;
 
     // ---- LDS-DMA (conv_march.h: every instruction is issued by every wave with all lanes on; the vmcnt immediates count instructions)
-    auto dma = [&](const char* src, const unsigned lds_byte) {
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_byte);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(m0v) : "memory");
-    };
+    auto dma = [&](const char* src, const unsigned lds_byte) { lds_dma16(src, lds_byte); };
     const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
     const unsigned bring_lds = smem_lds + 2u * PLANEQ * 16u;
-    const char* const zsrc = reinterpret_cast<const char*>(g_march_s2_zeros);
+    const char* const zsrc = reinterpret_cast<const char*>(g_lds_dma_zeros);
 
     // B: a step's 12 fragments f = (kw * 2 + hl) * 2 + n, 64 lanes x 16 B each.  Wave w fetches fragment w and fragment 8 + (w & 3)
     // (waves 4..7 repeat 8..11: the same bytes to the same slots, so that every wave issues exactly NIB instructions per step).
