@@ -10,7 +10,12 @@
 //  upsample+softmax+soft-argmin: the same g_d at full resolution, pushed back through the transposed
 //                      trilinear interpolation (8 corner weights) with float atomics into the low-res cost.
 // All are streaming kernels with lanes along w.
-#include "osa_common.h"
+//
+// The heads that also return the per-pixel variance (softargmin.hip) have two incoming gradients per pixel.  The logits form and the fold
+// pass of the fused form are ONE body each, `template <bool VAR>`, with the variance's share inside `if constexpr (VAR)`; the `__global__`
+// kernels are the named wrappers of the two instantiations.  The fused kernels open with the steps of head_common.h, which the forward
+// kernels run too: the recomputed samples are the forward's bit for bit.
+#include "head_common.h"
 
 namespace osa {
 
@@ -62,8 +67,13 @@ __global__ __launch_bounds__(256) void softargmin_bwd_kernel(const float* __rest
     dprob[i] = (float)d * dout[b * HW + hw];
 }
 
-__global__ __launch_bounds__(256) void softmax_softargmin_bwd_kernel(const float* __restrict__ cost, const float* __restrict__ dout,
-                                                                     float* __restrict__ dcost, int D, long long HW, long long total) {
+// logits (p = softmax, mu = sum p d, var = sum p (d - mu)^2), g / gv the gradients of the disparity / the variance:
+//     dcost[k] = p_k (k - mu) g                                 and with VAR   dcost[k] = p_k [ (k - mu) g + ((k - mu)^2 - var) gv ]
+// (the variance's dependence on its own mean drops out: sum_d p_d (d - mu) = 0).  One thread per pixel, serial over d: fixed order.
+template <bool VAR>
+__device__ __forceinline__ void softmax_softargmin_bwd_body(const float* __restrict__ cost, const float* __restrict__ dout,
+                                                            const float* __restrict__ dvar, float* __restrict__ dcost,
+                                                            int D, long long HW, long long total) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;    // over B*H*W
     if (i >= total) return;
     const long long b = i / HW, hw = i - b * HW;
@@ -73,78 +83,87 @@ __global__ __launch_bounds__(256) void softmax_softargmin_bwd_kernel(const float
     float se = 0.f, sd = 0.f;
     for (int d = 0; d < D; ++d) { const float e = expf(c[(size_t)d * HW] - m); se += e; sd = fmaf(e, (float)d, sd); }
     const float inv = 1.f / se, disp = sd * inv, g = dout[i];
+    float gv = 0.f, var = 0.f;
+    if constexpr (VAR) {
+        gv = dvar[i];
+        float sv = 0.f;
+        for (int d = 0; d < D; ++d) { const float t = (float)d - disp; sv = fmaf(expf(c[(size_t)d * HW] - m), t * t, sv); }
+        var = sv * inv;
+    }
     float* dc = dcost + (size_t)b * D * HW + hw;
-    for (int d = 0; d < D; ++d) dc[(size_t)d * HW] = expf(c[(size_t)d * HW] - m) * inv * ((float)d - disp) * g;
+    for (int d = 0; d < D; ++d) {
+        const float t = (float)d - disp, pd = expf(c[(size_t)d * HW] - m) * inv;
+        dc[(size_t)d * HW] = VAR ? pd * fmaf(t * t - var, gv, t * g) : pd * t * g;
+    }
 }
 
-__device__ __forceinline__ void src_index_b(int dst, float scale, int align, int in_size, int& i0, int& i1, float& l1) {
-    float s;
-    if (align) s = scale * (float)dst;
-    else { s = scale * ((float)dst + 0.5f) - 0.5f; s = s < 0.f ? 0.f : s; }
-    i0 = (int)s;
-    if (i0 > in_size - 1) i0 = in_size - 1;
-    i1 = i0 + ((i0 < in_size - 1) ? 1 : 0);
-    l1 = s - (float)i0;
+__global__ __launch_bounds__(256) void softmax_softargmin_bwd_kernel(const float* __restrict__ cost, const float* __restrict__ dout,
+                                                                     float* __restrict__ dcost, int D, long long HW, long long total) {
+    softmax_softargmin_bwd_body<false>(cost, dout, nullptr, dcost, D, HW, total);
+}
+__global__ __launch_bounds__(256) void softmax_softargmin_var_bwd_kernel(const float* __restrict__ cost, const float* __restrict__ dout,
+                                                                         const float* __restrict__ dvar, float* __restrict__ dcost,
+                                                                         int D, long long HW, long long total) {
+    softmax_softargmin_bwd_body<true>(cost, dout, dvar, dcost, D, HW, total);
 }
 
 struct UpBwdArgs {
-    const float* cost; const float* dout; float* dcost;   // dcost must be zero-initialised
-    int B, Dl, Hl, Wl, D, H, W, align;
-    float sd, sh, sw;
+    const float* cost; const float* dout; float* dcost;   // dcost must be zero-initialised (one-kernel form only)
+    UpDims g;
 };
+struct UpVarBwdArgs {
+    UpBwdArgs a;
+    const float* dvar;
+};
+
+// The backward's staging: the thread's Dl interpolated low-res costs into its column of cl[Dl][NT], as the forward's stage_column, with a zeroed
+// gradient column in gl[Dl][NT] beside it.  Returns the column's maximum (no sample exceeds it: the softmax's shift).
+template <int NT>
+__device__ __forceinline__ float stage_columns_bwd(const Bilinear<size_t>& f, const float* c, size_t plane, int Dl, float* cl, float* gl) {
+    const int tid = threadIdx.x;
+    float m = -INFINITY;
+    for (int dl = 0; dl < Dl; ++dl) {
+        const float v = f(c + (size_t)dl * plane);
+        cl[dl * NT + tid] = v; gl[dl * NT + tid] = 0.f;
+        m = fmaxf(m, v);
+    }
+    return m;
+}
 
 // one thread per output pixel: recompute its D up-sampled costs, softmax and disparity, fold
 // g_d = p_d (d - disp) dout along d into the Dl low-res planes (LDS, [dl][thread]), then add the 4
 // (y,x) corner contributions with float atomics.
 __global__ __launch_bounds__(256) void upsample_softargmin_bwd_kernel(const UpBwdArgs p) {
     extern __shared__ float sh[];            // cl[Dl][256] then gl[Dl][256]
-    float* cl = sh; float* gl = sh + (size_t)p.Dl * 256;
+    const UpDims& q = p.g;
+    float* cl = sh; float* gl = sh + (size_t)q.Dl * 256;
     const int tid = threadIdx.x;
-    const long long HW = (long long)p.H * p.W;
-    const long long i = (long long)blockIdx.x * 256 + tid;
-    const bool live = i < (long long)p.B * HW;
-    const long long ii = live ? i : 0;
-    const int b = (int)(ii / HW);
-    const int hw = (int)(ii - (long long)b * HW);
-    const int y = hw / p.W, x = hw - y * p.W;
-    int y0, y1, x0, x1; float ly, lx;
-    src_index_b(y, p.sh, p.align, p.Hl, y0, y1, ly);
-    src_index_b(x, p.sw, p.align, p.Wl, x0, x1, lx);
-    const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-    const size_t plane = (size_t)p.Hl * p.Wl;
-    const float* c = p.cost + (size_t)b * p.Dl * plane;
-    const size_t o00 = (size_t)y0 * p.Wl + x0, o01 = (size_t)y0 * p.Wl + x1, o10 = (size_t)y1 * p.Wl + x0, o11 = (size_t)y1 * p.Wl + x1;
-    float m = -INFINITY;
-    for (int dl = 0; dl < p.Dl; ++dl) {
-        const float* cp = c + (size_t)dl * plane;
-        const float v = w00 * cp[o00] + w01 * cp[o01] + w10 * cp[o10] + w11 * cp[o11];
-        cl[dl * 256 + tid] = v; gl[dl * 256 + tid] = 0.f;
-        m = fmaxf(m, v);
-    }
+    const UpPixel px = up_pixel<256>(q);
+    const Bilinear<size_t> f(px.y, px.x, q.sh, q.sw, q.align, q.Hl, q.Wl);
+    const size_t plane = (size_t)q.Hl * q.Wl;
+    const float m = stage_columns_bwd<256>(f, p.cost + (size_t)px.b * q.Dl * plane, plane, q.Dl, cl, gl);
     float se = 0.f, sdisp = 0.f;
-    for (int d = 0; d < p.D; ++d) {
-        int d0, d1; float ld;
-        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
-        const float e = expf((1.f - ld) * cl[d0 * 256 + tid] + ld * cl[d1 * 256 + tid] - m);
+    for (int d = 0; d < q.D; ++d) {
+        const float e = expf(up_sample<256>(cl, d, q) - m);
         se += e; sdisp = fmaf(e, (float)d, sdisp);
     }
     const float inv = 1.f / se, disp = sdisp * inv;
-    const float g = live ? p.dout[i] : 0.f;
-    for (int d = 0; d < p.D; ++d) {
+    const float g = px.live ? p.dout[px.i] : 0.f;
+    for (int d = 0; d < q.D; ++d) {
         int d0, d1; float ld;
-        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
-        const float e = expf((1.f - ld) * cl[d0 * 256 + tid] + ld * cl[d1 * 256 + tid] - m);
+        src_index(d, q.sd, q.align, q.Dl, d0, d1, ld);
+        const float e = expf((1.f - ld) * cl[d0 * 256 + tid] + ld * cl[d1 * 256 + tid] - m);    // up_sample(d), and where it came from
         const float gd = e * inv * ((float)d - disp) * g;
         gl[d0 * 256 + tid] += (1.f - ld) * gd;
         gl[d1 * 256 + tid] += ld * gd;
     }
-    if (!live) return;
-    float* dc = p.dcost + (size_t)b * p.Dl * plane;
-    for (int dl = 0; dl < p.Dl; ++dl) {
+    if (!px.live) return;
+    float* dc = p.dcost + (size_t)px.b * q.Dl * plane;
+    for (int dl = 0; dl < q.Dl; ++dl) {
         const float gv = gl[dl * 256 + tid];
         float* dp = dc + (size_t)dl * plane;
-        atomicAdd(dp + o00, w00 * gv); atomicAdd(dp + o01, w01 * gv);
-        atomicAdd(dp + o10, w10 * gv); atomicAdd(dp + o11, w11 * gv);
+        atomicAdd(dp + f.o00, f.w00 * gv); atomicAdd(dp + f.o01, f.w01 * gv);
+        atomicAdd(dp + f.o10, f.w10 * gv); atomicAdd(dp + f.o11, f.w11 * gv);
     }
 }
 
@@ -155,55 +174,58 @@ __global__ __launch_bounds__(256) void upsample_softargmin_bwd_kernel(const UpBw
 // pass 1 (fold): one thread per output pixel, as above, but the Dl folded gradients go to a scratch tensor G[b][dl][y][x] (coalesced).
 // pass 2 (gather): one thread per low-res cell sums w_y * w_x * G over the output pixels whose bilinear footprint contains the cell, in
 // a fixed order -- deterministic, no zero-fill, no atomics.
-template <int NT>
-__global__ __launch_bounds__(NT) void upsample_softargmin_bwd_fold_kernel(const UpBwdArgs p, float* __restrict__ G) {
+// VAR: the per-sample coefficient of the logits form above, with one more pass over the LDS-resident samples for the variance.
+template <int NT, bool VAR>
+__device__ __forceinline__ void upsample_softargmin_bwd_fold_body(const UpBwdArgs& p, const float* dvar, float* __restrict__ G) {
     extern __shared__ float sh[];            // cl[Dl][NT] then gl[Dl][NT]
-    float* cl = sh; float* gl = sh + (size_t)p.Dl * NT;
+    const UpDims& q = p.g;
+    float* cl = sh; float* gl = sh + (size_t)q.Dl * NT;
     const int tid = threadIdx.x;
-    const long long HW = (long long)p.H * p.W;
-    const long long i = (long long)blockIdx.x * NT + tid;
-    const bool live = i < (long long)p.B * HW;
-    const long long ii = live ? i : 0;
-    const int b = (int)(ii / HW);
-    const int hw = (int)(ii - (long long)b * HW);
-    const int y = hw / p.W, x = hw - y * p.W;
-    int y0, y1, x0, x1; float ly, lx;
-    src_index_b(y, p.sh, p.align, p.Hl, y0, y1, ly);
-    src_index_b(x, p.sw, p.align, p.Wl, x0, x1, lx);
-    const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-    const size_t plane = (size_t)p.Hl * p.Wl;
-    const float* c = p.cost + (size_t)b * p.Dl * plane;
-    const size_t o00 = (size_t)y0 * p.Wl + x0, o01 = (size_t)y0 * p.Wl + x1, o10 = (size_t)y1 * p.Wl + x0, o11 = (size_t)y1 * p.Wl + x1;
-    float m = -INFINITY;
-    for (int dl = 0; dl < p.Dl; ++dl) {
-        const float* cp = c + (size_t)dl * plane;
-        const float v = w00 * cp[o00] + w01 * cp[o01] + w10 * cp[o10] + w11 * cp[o11];
-        cl[dl * NT + tid] = v; gl[dl * NT + tid] = 0.f;
-        m = fmaxf(m, v);
-    }
+    const UpPixel px = up_pixel<NT>(q);
+    const Bilinear<size_t> f(px.y, px.x, q.sh, q.sw, q.align, q.Hl, q.Wl);
+    const size_t plane = (size_t)q.Hl * q.Wl;
+    const float m = stage_columns_bwd<NT>(f, p.cost + (size_t)px.b * q.Dl * plane, plane, q.Dl, cl, gl);
     float se = 0.f, sdisp = 0.f;
-    for (int d = 0; d < p.D; ++d) {
-        int d0, d1; float ld;
-        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
-        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);
+    for (int d = 0; d < q.D; ++d) {
+        const float e = expf(up_sample<NT>(cl, d, q) - m);
         se += e; sdisp = fmaf(e, (float)d, sdisp);
     }
     const float inv = 1.f / se, disp = sdisp * inv;
-    const float g = live ? p.dout[i] : 0.f;
-    for (int d = 0; d < p.D; ++d) {
+    float var = 0.f;
+    if constexpr (VAR) {
+        float sv = 0.f;
+        for (int d = 0; d < q.D; ++d) {
+            const float t = (float)d - disp;
+            sv = fmaf(expf(up_sample<NT>(cl, d, q) - m), t * t, sv);
+        }
+        var = sv * inv;
+    }
+    const float g = px.live ? p.dout[px.i] : 0.f, gv = (VAR && px.live) ? dvar[px.i] : 0.f;
+    for (int d = 0; d < q.D; ++d) {
         int d0, d1; float ld;
-        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
-        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);
-        const float gd = e * inv * ((float)d - disp) * g;
+        src_index(d, q.sd, q.align, q.Dl, d0, d1, ld);
+        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);    // up_sample(d), and where it came from
+        const float pd = e * inv, t = (float)d - disp;
+        const float gd = VAR ? pd * fmaf(t * t - var, gv, t * g) : pd * t * g;
         gl[d0 * NT + tid] += (1.f - ld) * gd;
         gl[d1 * NT + tid] += ld * gd;
     }
-    if (!live) return;
-    float* gp = G + (size_t)b * p.Dl * HW + hw;
-    for (int dl = 0; dl < p.Dl; ++dl) gp[(size_t)dl * HW] = gl[dl * NT + tid];
+    if (!px.live) return;
+    const long long HW = (long long)q.H * q.W;
+    float* gp = G + (size_t)px.b * q.Dl * HW + px.hw;
+    for (int dl = 0; dl < q.Dl; ++dl) gp[(size_t)dl * HW] = gl[dl * NT + tid];
 }
 
-// output positions whose source interval can contain low-res index `il` (a conservative range; the exact test is src_index_b)
+template <int NT>
+__global__ __launch_bounds__(NT) void upsample_softargmin_bwd_fold_kernel(const UpBwdArgs p, float* __restrict__ G) {
+    upsample_softargmin_bwd_fold_body<NT, false>(p, nullptr, G);
+}
+template <int NT>
+__global__ __launch_bounds__(NT) void upsample_softargmin_var_bwd_fold_kernel(const UpVarBwdArgs q, float* __restrict__ G) {
+    upsample_softargmin_bwd_fold_body<NT, true>(q.a, q.dvar, G);
+}
+
+// output positions whose source interval can contain low-res index `il` (a conservative range; the exact test is src_index)
 __device__ __forceinline__ void footprint(int il, float scale, int align, int out_size, int& lo, int& hi) {
     if (scale <= 0.f) { lo = 0; hi = out_size - 1; return; }
     const float off = align ? 0.f : 0.5f;
@@ -214,26 +236,26 @@ __device__ __forceinline__ void footprint(int il, float scale, int align, int ou
 }
 
 __global__ __launch_bounds__(256) void upsample_softargmin_bwd_gather_kernel(const UpBwdArgs p, const float* __restrict__ G) {
-    const long long total = (long long)p.B * p.Dl * p.Hl * p.Wl;
+    const long long total = (long long)p.g.B * p.g.Dl * p.g.Hl * p.g.Wl;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
-    const int xl = (int)(i % p.Wl); long long r = i / p.Wl;
-    const int yl = (int)(r % p.Hl); r /= p.Hl;               // r = b * Dl + dl
+    const int xl = (int)(i % p.g.Wl); long long r = i / p.g.Wl;
+    const int yl = (int)(r % p.g.Hl); r /= p.g.Hl;               // r = b * Dl + dl
     int ylo, yhi, xlo, xhi;
-    footprint(yl, p.sh, p.align, p.H, ylo, yhi);
-    footprint(xl, p.sw, p.align, p.W, xlo, xhi);
-    const float* g = G + (size_t)r * p.H * p.W;
+    footprint(yl, p.g.sh, p.g.align, p.g.H, ylo, yhi);
+    footprint(xl, p.g.sw, p.g.align, p.g.W, xlo, xhi);
+    const float* g = G + (size_t)r * p.g.H * p.g.W;
     float acc = 0.f;
     for (int y = ylo; y <= yhi; ++y) {
         int y0, y1; float ly;
-        src_index_b(y, p.sh, p.align, p.Hl, y0, y1, ly);
+        src_index(y, p.g.sh, p.g.align, p.g.Hl, y0, y1, ly);
         const float wy = ((y0 == yl) ? (1.f - ly) : 0.f) + ((y1 == yl) ? ly : 0.f);
         if (wy == 0.f) continue;
-        const float* gr = g + (size_t)y * p.W;
+        const float* gr = g + (size_t)y * p.g.W;
         float row = 0.f;
         for (int x = xlo; x <= xhi; ++x) {
             int x0, x1; float lx;
-            src_index_b(x, p.sw, p.align, p.Wl, x0, x1, lx);
+            src_index(x, p.g.sw, p.g.align, p.g.Wl, x0, x1, lx);
             const float wx = ((x0 == xl) ? (1.f - lx) : 0.f) + ((x1 == xl) ? lx : 0.f);
             row = fmaf(wx, gr[x], row);
         }
@@ -242,12 +264,9 @@ __global__ __launch_bounds__(256) void upsample_softargmin_bwd_gather_kernel(con
     p.dcost[i] = acc;
 }
 
-// ---- backward of the disparity + variance heads (softargmin.hip) ------------------------------------------------------------------------
+// ---- backward of the probabilities-form disparity + variance head (softargmin.hip) ------------------------------------------------------
 // Two incoming gradients per pixel: g of the disparity, gv of the variance.  One thread per pixel, serial over d: no atomics, fixed order.
 //  probabilities + given disparity `delta`:  dprob[d] = d g + (d - delta)^2 gv;   ddelta = -2 gv sum_d prob[d] (d - delta)
-//  logits (p = softmax, mu = sum p d, var = sum p (d - mu)^2):
-//                                            dcost[k] = p_k [ (k - mu) g + ((k - mu)^2 - var) gv ]
-//  (the variance's dependence on its own mean drops out: sum_d p_d (d - mu) = 0)
 __global__ __launch_bounds__(256) void softargmin_var_bwd_kernel(const float* __restrict__ prob, const float* __restrict__ disparity,
                                                                  const float* __restrict__ dout, const float* __restrict__ dvar,
                                                                  float* __restrict__ dprob, float* __restrict__ ddisp,
@@ -268,94 +287,6 @@ __global__ __launch_bounds__(256) void softargmin_var_bwd_kernel(const float* __
         dp[(size_t)d * HW] = (float)fma((double)d, g, t * t * gv);
     }
     ddisp[i] = (float)(-2.0 * gv * s);
-}
-
-__global__ __launch_bounds__(256) void softmax_softargmin_var_bwd_kernel(const float* __restrict__ cost, const float* __restrict__ dout,
-                                                                         const float* __restrict__ dvar, float* __restrict__ dcost,
-                                                                         int D, long long HW, long long total) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;    // over B*H*W
-    if (i >= total) return;
-    const long long b = i / HW, hw = i - b * HW;
-    const float* c = cost + (size_t)b * D * HW + hw;
-    float m = -INFINITY;
-    for (int d = 0; d < D; ++d) m = fmaxf(m, c[(size_t)d * HW]);
-    float se = 0.f, sd = 0.f;
-    for (int d = 0; d < D; ++d) { const float e = expf(c[(size_t)d * HW] - m); se += e; sd = fmaf(e, (float)d, sd); }
-    const float inv = 1.f / se, disp = sd * inv, g = dout[i], gv = dvar[i];
-    float sv = 0.f;
-    for (int d = 0; d < D; ++d) { const float t = (float)d - disp; sv = fmaf(expf(c[(size_t)d * HW] - m), t * t, sv); }
-    const float var = sv * inv;
-    float* dc = dcost + (size_t)b * D * HW + hw;
-    for (int d = 0; d < D; ++d) {
-        const float t = (float)d - disp;
-        dc[(size_t)d * HW] = expf(c[(size_t)d * HW] - m) * inv * fmaf(t * t - var, gv, t * g);
-    }
-}
-
-struct UpVarBwdArgs {
-    UpBwdArgs a;
-    const float* dvar;
-};
-
-// pass 1 of the two-pass form with the variance's gradient: upsample_softargmin_bwd_fold_kernel with the per-sample coefficient of the
-// logits form above (one more pass over the LDS-resident samples for the variance).  Pass 2 is upsample_softargmin_bwd_gather_kernel.
-template <int NT>
-__global__ __launch_bounds__(NT) void upsample_softargmin_var_bwd_fold_kernel(const UpVarBwdArgs q, float* __restrict__ G) {
-    extern __shared__ float sh[];            // cl[Dl][NT] then gl[Dl][NT]
-    const UpBwdArgs& p = q.a;
-    float* cl = sh; float* gl = sh + (size_t)p.Dl * NT;
-    const int tid = threadIdx.x;
-    const long long HW = (long long)p.H * p.W;
-    const long long i = (long long)blockIdx.x * NT + tid;
-    const bool live = i < (long long)p.B * HW;
-    const long long ii = live ? i : 0;
-    const int b = (int)(ii / HW);
-    const int hw = (int)(ii - (long long)b * HW);
-    const int y = hw / p.W, x = hw - y * p.W;
-    int y0, y1, x0, x1; float ly, lx;
-    src_index_b(y, p.sh, p.align, p.Hl, y0, y1, ly);
-    src_index_b(x, p.sw, p.align, p.Wl, x0, x1, lx);
-    const float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
-    const size_t plane = (size_t)p.Hl * p.Wl;
-    const float* c = p.cost + (size_t)b * p.Dl * plane;
-    const size_t o00 = (size_t)y0 * p.Wl + x0, o01 = (size_t)y0 * p.Wl + x1, o10 = (size_t)y1 * p.Wl + x0, o11 = (size_t)y1 * p.Wl + x1;
-    float m = -INFINITY;
-    for (int dl = 0; dl < p.Dl; ++dl) {
-        const float* cp = c + (size_t)dl * plane;
-        const float v = w00 * cp[o00] + w01 * cp[o01] + w10 * cp[o10] + w11 * cp[o11];
-        cl[dl * NT + tid] = v; gl[dl * NT + tid] = 0.f;
-        m = fmaxf(m, v);
-    }
-    float se = 0.f, sdisp = 0.f;
-    for (int d = 0; d < p.D; ++d) {
-        int d0, d1; float ld;
-        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
-        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);
-        se += e; sdisp = fmaf(e, (float)d, sdisp);
-    }
-    const float inv = 1.f / se, disp = sdisp * inv;
-    float sv = 0.f;
-    for (int d = 0; d < p.D; ++d) {
-        int d0, d1; float ld;
-        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
-        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);
-        const float t = (float)d - disp;
-        sv = fmaf(e, t * t, sv);
-    }
-    const float var = sv * inv;
-    const float g = live ? p.dout[i] : 0.f, gv = live ? q.dvar[i] : 0.f;
-    for (int d = 0; d < p.D; ++d) {
-        int d0, d1; float ld;
-        src_index_b(d, p.sd, p.align, p.Dl, d0, d1, ld);
-        const float e = expf((1.f - ld) * cl[d0 * NT + tid] + ld * cl[d1 * NT + tid] - m);
-        const float t = (float)d - disp;
-        const float gd = e * inv * fmaf(t * t - var, gv, t * g);
-        gl[d0 * NT + tid] += (1.f - ld) * gd;
-        gl[d1 * NT + tid] += ld * gd;
-    }
-    if (!live) return;
-    float* gp = G + (size_t)b * p.Dl * HW + hw;
-    for (int dl = 0; dl < p.Dl; ++dl) gp[(size_t)dl * HW] = gl[dl * NT + tid];
 }
 
 }  // namespace osa
@@ -414,9 +345,7 @@ extern "C" int osa_upsample_softargmin_bwd_f32(const float* cost_lowres, const f
     OSA_REQUIRE(lds <= 160 * 1024, "upsample_softargmin_bwd: Dl=%d too large for LDS", Dl);
     UpBwdArgs a;
     a.cost = cost_lowres; a.dout = dout; a.dcost = dcost_lowres;
-    a.B = B; a.Dl = Dl; a.Hl = Hl; a.Wl = Wl; a.D = D; a.H = H; a.W = W; a.align = align_corners ? 1 : 0;
-    auto sc = [&](int in, int out) { return a.align ? ((out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f) : (float)in / (float)out; };
-    a.sd = sc(Dl, D); a.sh = sc(Hl, H); a.sw = sc(Wl, W);
+    a.g = up_dims(B, Dl, Hl, Wl, D, H, W, align_corners);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(dcost_lowres, 0, (size_t)B * Dl * Hl * Wl * sizeof(float), st);
     OSA_REQUIRE(e == hipSuccess, "upsample_softargmin_bwd: memset failed: %s", hipGetErrorString(e));
@@ -433,29 +362,38 @@ extern "C" size_t osa_upsample_softargmin_bwd_workspace_bytes(int B, int Dl, int
     return (size_t)B * Dl * H * W * sizeof(float);
 }
 
+// the two-pass form with (dvar != NULL) or without the variance's gradient: its fold pass, then the gather pass both share
+static int launch_upsample_softargmin_bwd_ws(const float* cost_lowres, const float* dout, const float* dvar, float* dcost_lowres,
+                                             int B, int Dl, int Hl, int Wl, int D, int H, int W,
+                                             int align_corners, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    const char* name = dvar ? "upsample_softargmin_var_bwd_ws" : "upsample_softargmin_bwd_ws";
+    OSA_REQUIRE(workspace_bytes >= osa_upsample_softargmin_bwd_workspace_bytes(B, Dl, H, W) && ((size_t)workspace & 15) == 0,
+                "%s: workspace too small or misaligned (osa_upsample_softargmin_bwd_workspace_bytes)", name);
+    constexpr int NT = 128;
+    const size_t lds = (size_t)Dl * NT * sizeof(float) * 2;
+    OSA_REQUIRE(lds <= 160 * 1024, "%s: Dl=%d too large for LDS", name, Dl);
+    UpVarBwdArgs q;
+    UpBwdArgs& a = q.a;
+    a.cost = cost_lowres; a.dout = dout; a.dcost = dcost_lowres; q.dvar = dvar;
+    a.g = up_dims(B, Dl, Hl, Wl, D, H, W, align_corners);
+    const void* fold = dvar ? (const void*)upsample_softargmin_var_bwd_fold_kernel<NT> : (const void*)upsample_softargmin_bwd_fold_kernel<NT>;
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    float* G = static_cast<float*>(workspace);
+    const dim3 grid(cdiv((long long)B * H * W, NT));
+    if (dvar) hipLaunchKernelGGL(upsample_softargmin_var_bwd_fold_kernel<NT>, grid, dim3(NT), lds, st, q, G);
+    else hipLaunchKernelGGL(upsample_softargmin_bwd_fold_kernel<NT>, grid, dim3(NT), lds, st, a, G);
+    OSA_LAUNCH_CHECK(dvar ? "upsample_softargmin_var_bwd_ws (fold)" : "upsample_softargmin_bwd_ws (fold)");
+    hipLaunchKernelGGL(upsample_softargmin_bwd_gather_kernel, dim3(cdiv((long long)B * Dl * Hl * Wl, 256)), dim3(256), 0, st, a, (const float*)G);
+    OSA_LAUNCH_CHECK(dvar ? "upsample_softargmin_var_bwd_ws (gather)" : "upsample_softargmin_bwd_ws (gather)");
+    return 0;
+}
+
 extern "C" int osa_upsample_softargmin_bwd_ws_f32(const float* cost_lowres, const float* dout, float* dcost_lowres,
                                                   int B, int Dl, int Hl, int Wl, int D, int H, int W,
                                                   int align_corners, void* workspace, size_t workspace_bytes, void* stream) {
     OSA_REQUIRE(cost_lowres && dout && dcost_lowres && workspace, "upsample_softargmin_bwd_ws: NULL pointer");
-    OSA_REQUIRE(workspace_bytes >= osa_upsample_softargmin_bwd_workspace_bytes(B, Dl, H, W) && ((size_t)workspace & 15) == 0,
-                "upsample_softargmin_bwd_ws: workspace too small or misaligned (osa_upsample_softargmin_bwd_workspace_bytes)");
-    constexpr int NT = 128;
-    const size_t lds = (size_t)Dl * NT * sizeof(float) * 2;
-    OSA_REQUIRE(lds <= 160 * 1024, "upsample_softargmin_bwd_ws: Dl=%d too large for LDS", Dl);
-    UpBwdArgs a;
-    a.cost = cost_lowres; a.dout = dout; a.dcost = dcost_lowres;
-    a.B = B; a.Dl = Dl; a.Hl = Hl; a.Wl = Wl; a.D = D; a.H = H; a.W = W; a.align = align_corners ? 1 : 0;
-    auto sc = [&](int in, int out) { return a.align ? ((out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f) : (float)in / (float)out; };
-    a.sd = sc(Dl, D); a.sh = sc(Hl, H); a.sw = sc(Wl, W);
-    hipStream_t st = (hipStream_t)stream;
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)upsample_softargmin_bwd_fold_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    float* G = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(upsample_softargmin_bwd_fold_kernel<NT>, dim3(cdiv((long long)B * H * W, NT)), dim3(NT), lds, st, a, G);
-    OSA_LAUNCH_CHECK("upsample_softargmin_bwd_ws (fold)");
-    hipLaunchKernelGGL(upsample_softargmin_bwd_gather_kernel, dim3(cdiv((long long)B * Dl * Hl * Wl, 256)), dim3(256), 0, st, a, (const float*)G);
-    OSA_LAUNCH_CHECK("upsample_softargmin_bwd_ws (gather)");
-    return 0;
+    return launch_upsample_softargmin_bwd_ws(cost_lowres, dout, nullptr, dcost_lowres, B, Dl, Hl, Wl, D, H, W, align_corners,
+                                             workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- disparity + variance heads ---------------------------------------------------------------------------------------------------
@@ -486,25 +424,6 @@ extern "C" int osa_upsample_softargmin_var_bwd_ws_f32(const float* cost_lowres, 
                                                       int align_corners, void* workspace, size_t workspace_bytes, void* stream) {
     OSA_REQUIRE(cost_lowres && dout && dvar && dcost_lowres && workspace, "upsample_softargmin_var_bwd_ws: NULL pointer");
     OSA_REQUIRE(B > 0 && Dl > 0 && Hl > 0 && Wl > 0 && D > 0 && H > 0 && W > 0, "upsample_softargmin_var_bwd_ws: bad dims");
-    OSA_REQUIRE(workspace_bytes >= osa_upsample_softargmin_bwd_workspace_bytes(B, Dl, H, W) && ((size_t)workspace & 15) == 0,
-                "upsample_softargmin_var_bwd_ws: workspace too small or misaligned (osa_upsample_softargmin_bwd_workspace_bytes)");
-    constexpr int NT = 128;
-    const size_t lds = (size_t)Dl * NT * sizeof(float) * 2;
-    OSA_REQUIRE(lds <= 160 * 1024, "upsample_softargmin_var_bwd_ws: Dl=%d too large for LDS", Dl);
-    UpVarBwdArgs q;
-    UpBwdArgs& a = q.a;
-    a.cost = cost_lowres; a.dout = dout; a.dcost = dcost_lowres;
-    a.B = B; a.Dl = Dl; a.Hl = Hl; a.Wl = Wl; a.D = D; a.H = H; a.W = W; a.align = align_corners ? 1 : 0;
-    auto sc = [&](int in, int out) { return a.align ? ((out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f) : (float)in / (float)out; };
-    a.sd = sc(Dl, D); a.sh = sc(Hl, H); a.sw = sc(Wl, W);
-    q.dvar = dvar;
-    hipStream_t st = (hipStream_t)stream;
-    if (lds > 64 * 1024)
-        (void)hipFuncSetAttribute((const void*)upsample_softargmin_var_bwd_fold_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    float* G = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(upsample_softargmin_var_bwd_fold_kernel<NT>, dim3(cdiv((long long)B * H * W, NT)), dim3(NT), lds, st, q, G);
-    OSA_LAUNCH_CHECK("upsample_softargmin_var_bwd_ws (fold)");
-    hipLaunchKernelGGL(upsample_softargmin_bwd_gather_kernel, dim3(cdiv((long long)B * Dl * Hl * Wl, 256)), dim3(256), 0, st, a, (const float*)G);
-    OSA_LAUNCH_CHECK("upsample_softargmin_var_bwd_ws (gather)");
-    return 0;
+    return launch_upsample_softargmin_bwd_ws(cost_lowres, dout, dvar, dcost_lowres, B, Dl, Hl, Wl, D, H, W, align_corners,
+                                             workspace, workspace_bytes, (hipStream_t)stream);
 }
