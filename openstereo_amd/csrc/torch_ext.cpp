@@ -341,30 +341,45 @@ std::tuple<at::Tensor, bool> cost_volume_cl(const at::Tensor& gwc_feat, const c1
 // dims: [B, D, H, W, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed].  prec: 0 exact
 // fp32, 1 f16x3 (x_meta / dy_meta required), 2 native f16 (metas optional).  Returns false when the split-precision forms do not cover the layer
 // (the caller then asks for prec 0); dw is written in place ([Co][Ci][k] or, transposed, [Ci][Co][k]).
+// workspace bytes of form `prec` for `dims`, 0 when the form does not cover the layer: host arithmetic, no pointer is touched.  d = dims as ints
+static size_t wgrad_workspace(at::IntArrayRef dims, int64_t prec, const char* who, const char* batch, int (&d)[22]) {
+    TORCH_CHECK(dims.size() == 22, who, ": dims = [", batch, ", D, H, W, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad x3, dil x3, transposed]");
+    for (int i = 0; i < 22; ++i) d[i] = (int)dims[i];
+    const auto query = prec == 0 ? osa_conv3d_wgrad_workspace_bytes : osa_conv3d_wgrad_f16x3_workspace_bytes;       // (they take no strides)
+    return query(d[0], d[1], d[2], d[3], d[4], d[6], d[7], d[8], d[9], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21]);
+}
+struct WgradOperands {
+    std::vector<const void*> x, dy;       // one pointer each, or (list) the items of conv_wgrad_multi
+    bool list, xh, dyh;                   // xh / dyh: the tensors hold fp16 elements
+};
+// conv_wgrad and conv_wgrad_multi once they have checked and collected their tensors
+static bool wgrad_run(const char* who, const char* batch, const WgradOperands& t, at::Tensor& dw, at::IntArrayRef dims, int64_t prec,
+                      const c10::optional<at::Tensor>& x_meta, const c10::optional<at::Tensor>& dy_meta) {
+    TORCH_CHECK(prec == 2 || (!t.xh && !t.dyh), who, ": fp16 tensors exist in the native f16 form only (prec 2)");
+    int d[22];
+    const size_t need = wgrad_workspace(dims, prec, who, batch, d);
+    if (need == 0) {
+        TORCH_CHECK(prec != 0, who, ": unsupported layer");
+        return false;
+    }
+    auto ws = at::empty({(int64_t)((need + 3) / 4)}, dw.options());
+    void* st = cur_stream();
+    const float* const x = static_cast<const float*>(t.x[0]); const float* const dy = static_cast<const float*>(t.dy[0]);
+#define OSA_WG_DIMS d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21]
+    if (t.list) OSA_CALL(osa_conv3d_wgrad_ws_multi((int)prec, t.x.data(), t.dy.data(), (int)t.x.size(), dw.data_ptr<float>(), OSA_WG_DIMS, fpo(x_meta), fpo(dy_meta),
+                                                   t.xh ? 1 : 0, t.dyh ? 1 : 0, ws.data_ptr<float>(), need, st));
+    else if (prec == 0) OSA_CALL(osa_conv3d_wgrad_ws_f32(x, dy, dw.data_ptr<float>(), OSA_WG_DIMS, ws.data_ptr<float>(), need, st));
+    else if (prec == 1) OSA_CALL(osa_conv3d_wgrad_ws_f16x3(x, dy, dw.data_ptr<float>(), OSA_WG_DIMS, fpo(x_meta), fpo(dy_meta), ws.data_ptr<float>(), need, st));
+    else OSA_CALL(osa_conv3d_wgrad_ws_f16(x, dy, dw.data_ptr<float>(), OSA_WG_DIMS, fpo(x_meta), fpo(dy_meta), t.xh ? 1 : 0, t.dyh ? 1 : 0, ws.data_ptr<float>(), need, st));
+#undef OSA_WG_DIMS
+    return true;
+}
 bool conv_wgrad(const at::Tensor& x, const at::Tensor& dy, at::Tensor dw, at::IntArrayRef dims, int64_t prec, const c10::optional<at::Tensor>& x_meta,
                 const c10::optional<at::Tensor>& dy_meta) {
     gpu_f32(dw, "dw");
     const bool xh = x.scalar_type() == at::kHalf, dyh = dy.scalar_type() == at::kHalf;
     TORCH_CHECK(x.is_cuda() && dy.is_cuda() && (xh || x.scalar_type() == at::kFloat) && (dyh || dy.scalar_type() == at::kFloat), "conv_wgrad: x / dy must be CUDA fp32 or fp16 tensors");
-    TORCH_CHECK(prec == 2 || (!xh && !dyh), "conv_wgrad: fp16 tensors exist in the native f16 form only (prec 2)");
-    TORCH_CHECK(dims.size() == 22, "conv_wgrad: dims = [B, D, H, W, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad x3, dil x3, transposed]");
-    int d[22];
-    for (int i = 0; i < 22; ++i) d[i] = (int)dims[i];
-    const size_t need = prec == 0
-        ? osa_conv3d_wgrad_workspace_bytes(d[0], d[1], d[2], d[3], d[4], d[6], d[7], d[8], d[9], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21])
-        : osa_conv3d_wgrad_f16x3_workspace_bytes(d[0], d[1], d[2], d[3], d[4], d[6], d[7], d[8], d[9], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21]);
-    if (need == 0) {
-        TORCH_CHECK(prec != 0, "conv_wgrad: unsupported layer");
-        return false;
-    }
-    auto ws = at::empty({(int64_t)((need + 3) / 4)}, dw.options());
-    void* st = cur_stream();
-#define OSA_WG_ARGS static_cast<const float*>(x.data_ptr()), static_cast<const float*>(dy.data_ptr()), dw.data_ptr<float>(), d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21]
-    if (prec == 0) OSA_CALL(osa_conv3d_wgrad_ws_f32(OSA_WG_ARGS, ws.data_ptr<float>(), need, st));
-    else if (prec == 1) OSA_CALL(osa_conv3d_wgrad_ws_f16x3(OSA_WG_ARGS, fpo(x_meta), fpo(dy_meta), ws.data_ptr<float>(), need, st));
-    else OSA_CALL(osa_conv3d_wgrad_ws_f16(OSA_WG_ARGS, fpo(x_meta), fpo(dy_meta), xh ? 1 : 0, dyh ? 1 : 0, ws.data_ptr<float>(), need, st));
-#undef OSA_WG_ARGS
-    return true;
+    return wgrad_run("conv_wgrad", "B", {{x.data_ptr()}, {dy.data_ptr()}, false, xh, dyh}, dw, dims, prec, x_meta, dy_meta);
 }
 
 // the same over a LIST of equally shaped (x, dy) pairs in one launch (osa_conv3d_wgrad_ws_multi): dims[0] = the TOTAL batch over all items
@@ -372,31 +387,15 @@ bool conv_wgrad_multi(at::TensorList xs, at::TensorList dys, at::Tensor dw, at::
                       const c10::optional<at::Tensor>& dy_meta) {
     gpu_f32(dw, "dw");
     TORCH_CHECK(xs.size() >= 1 && xs.size() <= 24 && xs.size() == dys.size(), "conv_wgrad_multi: 1..24 (x, dy) pairs");
-    const bool xh = xs[0].scalar_type() == at::kHalf, dyh = dys[0].scalar_type() == at::kHalf;
-    std::vector<const void*> xp, dp;
+    WgradOperands t{{}, {}, true, xs[0].scalar_type() == at::kHalf, dys[0].scalar_type() == at::kHalf};
     for (size_t i = 0; i < xs.size(); ++i) {
         TORCH_CHECK(xs[i].is_cuda() && dys[i].is_cuda() && xs[i].scalar_type() == xs[0].scalar_type() && dys[i].scalar_type() == dys[0].scalar_type() &&
                     xs[i].sizes() == xs[0].sizes() && xs[i].strides() == xs[0].strides() && dys[i].sizes() == dys[0].sizes() && dys[i].strides() == dys[0].strides(),
                     "conv_wgrad_multi: the items must agree in device, dtype, shape and strides");
-        xp.push_back(xs[i].data_ptr()); dp.push_back(dys[i].data_ptr());
+        t.x.push_back(xs[i].data_ptr()); t.dy.push_back(dys[i].data_ptr());
     }
-    TORCH_CHECK((xh || xs[0].scalar_type() == at::kFloat) && (dyh || dys[0].scalar_type() == at::kFloat), "conv_wgrad_multi: fp32 or fp16 tensors");
-    TORCH_CHECK(prec == 2 || (!xh && !dyh), "conv_wgrad_multi: fp16 tensors exist in the native f16 form only (prec 2)");
-    TORCH_CHECK(dims.size() == 22, "conv_wgrad_multi: dims = [B total, D, H, W, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad x3, dil x3, transposed]");
-    int d[22];
-    for (int i = 0; i < 22; ++i) d[i] = (int)dims[i];
-    const size_t need = prec == 0
-        ? osa_conv3d_wgrad_workspace_bytes(d[0], d[1], d[2], d[3], d[4], d[6], d[7], d[8], d[9], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21])
-        : osa_conv3d_wgrad_f16x3_workspace_bytes(d[0], d[1], d[2], d[3], d[4], d[6], d[7], d[8], d[9], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21]);
-    if (need == 0) {
-        TORCH_CHECK(prec != 0, "conv_wgrad_multi: unsupported layer");
-        return false;
-    }
-    auto ws = at::empty({(int64_t)((need + 3) / 4)}, dw.options());
-    OSA_CALL(osa_conv3d_wgrad_ws_multi((int)prec, xp.data(), dp.data(), (int)xs.size(), dw.data_ptr<float>(), d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10],
-                                       d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21], fpo(x_meta), fpo(dy_meta), xh ? 1 : 0, dyh ? 1 : 0,
-                                       ws.data_ptr<float>(), need, cur_stream()));
-    return true;
+    TORCH_CHECK((t.xh || xs[0].scalar_type() == at::kFloat) && (t.dyh || dys[0].scalar_type() == at::kFloat), "conv_wgrad_multi: fp32 or fp16 tensors");
+    return wgrad_run("conv_wgrad_multi", "B total", t, dw, dims, prec, x_meta, dy_meta);
 }
 
 // ---- layout, packing, ConvGRU gates, geometry-encoding lookup: the remaining per-step launches of the training path --------------------
@@ -1083,12 +1082,8 @@ std::tuple<at::Tensor, bool> cost_volume_cl_meta(const at::Tensor& gwc_feat, con
 // conv_wgrad: whether the requested form covers the layer is the workspace query's answer (host arithmetic on dims)
 bool conv_wgrad_meta(const at::Tensor& x, const at::Tensor& dy, at::Tensor dw, at::IntArrayRef dims, int64_t prec, const c10::optional<at::Tensor>& x_meta,
                      const c10::optional<at::Tensor>& dy_meta) {
-    TORCH_CHECK(dims.size() == 22, "conv_wgrad: dims = [B, D, H, W, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad x3, dil x3, transposed]");
     int d[22];
-    for (int i = 0; i < 22; ++i) d[i] = (int)dims[i];
-    const size_t need = prec == 0
-        ? osa_conv3d_wgrad_workspace_bytes(d[0], d[1], d[2], d[3], d[4], d[6], d[7], d[8], d[9], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21])
-        : osa_conv3d_wgrad_f16x3_workspace_bytes(d[0], d[1], d[2], d[3], d[4], d[6], d[7], d[8], d[9], d[11], d[12], d[13], d[14], d[15], d[16], d[17], d[18], d[19], d[20], d[21]);
+    const size_t need = wgrad_workspace(dims, prec, "conv_wgrad", "B", d);
     TORCH_CHECK(need != 0 || prec != 0, "conv_wgrad: unsupported layer");
     (void)x; (void)dy; (void)dw; (void)x_meta; (void)dy_meta;
     return need != 0;

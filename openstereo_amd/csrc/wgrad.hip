@@ -21,6 +21,7 @@
 #include "osa_common.h"
 #include <cstring>
 #include <cstddef>
+#include <type_traits>
 
 namespace osa {
 
@@ -66,6 +67,19 @@ __device__ __forceinline__ const void* wg_tab(size_t table_offset, int i) {
     typedef const char __attribute__((address_space(4))) kchar;
     kchar* ka = (kchar*)__builtin_amdgcn_kernarg_segment_ptr();
     return *reinterpret_cast<const void* const __attribute__((address_space(4)))*>(ka + table_offset + (size_t)i * sizeof(void*));
+}
+
+__device__ __forceinline__ void wg_zero(f32x16 (&acc)[WG_TAPS]) {
+#pragma unroll
+    for (int t = 0; t < WG_TAPS; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+}
+// batch entry b of the launch = entry bl of the tensors at Pbase / Qbase: item b / bper of the list, or the one tensor
+__device__ __forceinline__ void wg_batch_item(const WgradArgs& p, int b, int& bl, const float*& Pbase, const float*& Qbase) {
+    bl = p.ntab ? b % p.bper : b;
+    Pbase = p.ntab ? static_cast<const float*>(wg_tab(offsetof(WgradArgs, Ptab), b / p.bper)) : p.P;
+    Qbase = p.ntab ? static_cast<const float*>(wg_tab(offsetof(WgradArgs, Qtab), b / p.bper)) : p.Q;
 }
 
 template <int TD, int TH, int TW>     // position brick, TD*TH*TW = 256 (64 per wave) or 64 (16 per wave)
@@ -212,8 +226,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const WgradArgs p) {
 // positions.  Staging transposes: a thread takes (two w-neighbours, four channels), converts, and writes 32-bit hi / lo pairs.
 // A tap's Q operand is the same row shifted by dh rows and dw = 0..2 halves; rows are padded to 16-byte multiples, one ds_read_b128 +
 // one ds_read_b32 per row and plane serve all three dw (dw = 0: as read, dw = 1: v_alignbit by 16, dw = 2: the next dwords).
-// Unit stride, unit dilation, tap groups = one kd plane (<= 9 taps); 128-position bricks (2x8x8, flat 1x8x16): 59 / 49 KB of LDS, 2 / 3
-// workgroups per CU.  Same accumulator layout, workspace records and reduce kernel as the fp32 form.
+// Unit stride, unit dilation, tap groups = one kd plane (<= 9 taps); 128-position bricks (2x8x8, flat 1x8x16): 59 / 49 KB of LDS (the
+// registers, 178 VGPRs + 144 AGPRs = one wave per SIMD, allow ONE workgroup per CU).  Same accumulator layout, workspace records and reduce kernel as the fp32 form.
 typedef _Float16 wf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 wf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float wg_pow2_scale(float amax) {              // = pow2_scale of conv_kernel.h: amax * s in [2^14, 2^15)
@@ -236,6 +250,106 @@ __device__ __forceinline__ void wg_split2(float x0, float x1, unsigned& hi, unsi
     hi = __builtin_bit_cast(unsigned, h); lo = __builtin_bit_cast(unsigned, l);
 }
 
+// ---- what the single-tile and the multi-tile kernel of the f16 family share: LDS layout, staging loads, commit, one Q row of taps -------
+// LDS images of a TD x TH x TW position brick whose Q brick holds TDQ planes.  The kernels index with it and the host sizes the dynamic
+// LDS with it (wg_f16_lds): one definition, so the launch bytes cannot drift from the layout.
+template <int TD, int TH, int TW, int TDQ = TD>
+struct WgF16Layout {
+    static_assert(TD * TH * TW == 128 && (TW == 8 || TW == 16), "128-position bricks");
+    static constexpr int ROWH = (TW == 8) ? 16 : 24;        // halves per Q row in LDS (LW <= TW + 2, padded to a 16-byte multiple)
+    static constexpr int LHM = TH + 2;                      // Q rows per plane in LDS (host: at most 2 halo rows)
+    static constexpr int CHS_P = 136;                       // halves per channel (128 positions + 8: 16-byte rows of consecutive channels on distinct slots)
+    static constexpr int CHS_Q = TDQ * LHM * ROWH + 8;      // 328 / 248 (TDQ = TD + 2: 648)
+    static_assert((CHS_P / 8) % 2 == 1 && (CHS_Q / 8) % 2 == 1, "odd number of 16-byte slots per channel");
+    // bytes of the operand images of na x nb 32-channel tiles in `planes` planes (hi, or hi and lo)
+    static constexpr size_t lds_bytes(int planes, int na, int nb) { return (size_t)planes * (na * 32 * CHS_P + nb * 32 * CHS_Q) * sizeof(unsigned short); }
+};
+// four channels of one position of a tensor of fp32 or (F16 = 1: native f16 form, channel stride % 4 == 0) fp16 elements; nc = channels
+// left in the tensor
+template <int F16> struct WgElem { typedef float type; };
+template <> struct WgElem<1> { typedef _Float16 type; };
+template <int F16>
+__device__ __forceinline__ float4 wg_load4(const typename WgElem<F16>::type* src, int nc, bool ok) {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ok) {
+        if constexpr (F16) {
+            if (nc >= 4) {
+                const uint2 u = *reinterpret_cast<const uint2*>(src);
+                const wf16x2 a = __builtin_bit_cast(wf16x2, u.x), c = __builtin_bit_cast(wf16x2, u.y);
+                v = make_float4((float)a[0], (float)a[1], (float)c[0], (float)c[1]);
+            } else { if (nc > 0) v.x = (float)src[0]; if (nc > 1) v.y = (float)src[1]; if (nc > 2) v.z = (float)src[2]; }
+        } else {
+            if (nc >= 4) v = *reinterpret_cast<const float4*>(src);
+            else { if (nc > 0) v.x = src[0]; if (nc > 1) v.y = src[1]; if (nc > 2) v.z = src[2]; }
+        }
+    }
+    return v;
+}
+// the two w-neighbours of one staging item: ELEMENT offset `off` of the batch item and `step` elements further (PCs, QCs, class mode 2 QCs)
+template <int F16>
+__device__ __forceinline__ void wg_load_pair(float4 (&v)[2], const float* base, size_t off, int step, int nc, bool ok0, bool ok1) {
+    const typename WgElem<F16>::type* src = reinterpret_cast<const typename WgElem<F16>::type*>(base) + off;
+    v[0] = wg_load4<F16>(src, nc, ok0);
+    v[1] = wg_load4<F16>(src + step, nc, ok1);
+}
+// registers -> scaled fp16 hi (/ lo) pairs in LDS: items v[k] to halves dst[k] + j * CHS of channel j; ok = NULL: every item exists
+template <int SPLIT, int CHS, int N>
+__device__ __forceinline__ void wg_commit(unsigned short* hi, unsigned short* lo, const int (&dst)[N], const unsigned* ok, const float4 (&v)[N][2], float scale) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        if (ok && !ok[k]) continue;
+        const float x0[4] = {v[k][0].x, v[k][0].y, v[k][0].z, v[k][0].w}, x1[4] = {v[k][1].x, v[k][1].y, v[k][1].z, v[k][1].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if constexpr (SPLIT) {
+                unsigned h, l;
+                wg_split2(x0[j] * scale, x1[j] * scale, h, l);
+                *reinterpret_cast<unsigned*>(hi + dst[k] + j * CHS) = h;
+                *reinterpret_cast<unsigned*>(lo + dst[k] + j * CHS) = l;
+            } else *reinterpret_cast<unsigned*>(hi + dst[k] + j * CHS) = wg_round2(x0[j] * scale, x1[j] * scale);
+        }
+    }
+}
+// Row dh of the 3 x 3 slots of tap group tg, if the group has a tap there (uniform over the workgroup): N P operands ah / al (8 positions
+// of one channel per lane) against the Q rows of the same positions, at qrow_h / qrow_l + qoff[i] in the hi / lo plane.  One 128-bit and one
+// 32-bit read per plane serve the three taps dw (dw = 0: as read, dw = 1: v_alignbit by 16, dw = 2: the next dwords); 3 MFMAs per tap with
+// SPLIT, 1 without, into slot dh * 3 + dw.  The row test lives here, beside the tap tests: tested in the kernels, in front of a helper
+// without it, the compiler merged the slot loads of the single-tile kernel differently (profiles/round9/wgrad_one_definition.md).
+template <int SPLIT, int N>
+__device__ __forceinline__ void wg_tap_row(f32x16 (&acc)[WG_TAPS], const WgradArgs& p, int tg, int dh, const uint4* ah, const uint4* al,
+                                           const unsigned short* qrow_h, const unsigned short* qrow_l, const int* qoff) {
+    if (p.g_slot[tg][dh * 3] >= 0 || p.g_slot[tg][dh * 3 + 1] >= 0 || p.g_slot[tg][dh * 3 + 2] >= 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const unsigned short* qh = qrow_h + qoff[i];
+            const unsigned short* ql = qrow_l + qoff[i];
+            const uint4 vh = *reinterpret_cast<const uint4*>(qh), vl = SPLIT ? *reinterpret_cast<const uint4*>(ql) : vh;
+            const unsigned eh = *reinterpret_cast<const unsigned*>(qh + 8), el = SPLIT ? *reinterpret_cast<const unsigned*>(ql + 8) : eh;
+            const wf16x8 pa_h = __builtin_bit_cast(wf16x8, ah[i]), pa_l = __builtin_bit_cast(wf16x8, al[i]);
+#pragma unroll
+            for (int dw = 0; dw < 3; ++dw) {
+                if (p.g_slot[tg][dh * 3 + dw] >= 0) {
+                    uint4 bh, bl;
+                    if (dw == 0) { bh = vh; bl = vl; }
+                    else if (dw == 1) {
+                        bh = make_uint4(__builtin_amdgcn_alignbit(vh.y, vh.x, 16), __builtin_amdgcn_alignbit(vh.z, vh.y, 16),
+                                        __builtin_amdgcn_alignbit(vh.w, vh.z, 16), __builtin_amdgcn_alignbit(eh, vh.w, 16));
+                        bl = make_uint4(__builtin_amdgcn_alignbit(vl.y, vl.x, 16), __builtin_amdgcn_alignbit(vl.z, vl.y, 16),
+                                        __builtin_amdgcn_alignbit(vl.w, vl.z, 16), __builtin_amdgcn_alignbit(el, vl.w, 16));
+                    } else { bh = make_uint4(vh.y, vh.z, vh.w, eh); bl = make_uint4(vl.y, vl.z, vl.w, el); }
+                    const wf16x8 qb_h = __builtin_bit_cast(wf16x8, bh), qb_l = __builtin_bit_cast(wf16x8, bl);
+                    f32x16& c = acc[dh * 3 + dw];
+                    if constexpr (SPLIT) {
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_h, qb_l, c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_l, qb_h, c, 0, 0, 0);
+                    }
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_h, qb_h, c, 0, 0, 0);
+                }
+            }
+        }
+    }
+}
+
 // SPLIT = 1: the f16x3 form above.  SPLIT = 0 (r5): the native f16 form -- the arithmetic of the reference's AMP training
 // (trainer_template.py:211-226: autocast + GradScaler; the weight gradient of an autocast convolution multiplies fp16 activations by
 // fp16 output gradients and accumulates in fp32): operands rounded to fp16 (nearest even) when they are staged, ONE MFMA per product, no
@@ -245,12 +359,8 @@ __device__ __forceinline__ void wg_split2(float x0, float x1, unsigned& hi, unsi
 template <int TD, int TH, int TW, int SPLIT, int PF16 = 0, int QF16 = 0>     // 128 positions: 2x8x8 or (flat) 1x8x16
 __global__ __launch_bounds__(256) void wgrad_f16x3_kernel(const WgradArgs p) {
     static_assert(!SPLIT || (!PF16 && !QF16), "fp16 tensors exist in the native f16 form only");
-    static_assert(TD * TH * TW == 128 && (TW == 8 || TW == 16), "128-position bricks");
-    constexpr int ROWH = (TW == 8) ? 16 : 24;        // halves per Q row in LDS (LW <= TW + 2, padded to a 16-byte multiple)
-    constexpr int LHM = TH + 2;                      // Q rows per plane in LDS (host: at most 2 halo rows)
-    constexpr int CHS_P = 136;                       // halves per channel (128 positions + 8: 16-byte rows of consecutive channels on distinct slots)
-    constexpr int CHS_Q = TD * LHM * ROWH + 8;       // 328 / 248
-    static_assert((CHS_P / 8) % 2 == 1 && (CHS_Q / 8) % 2 == 1, "odd number of 16-byte slots per channel");
+    typedef WgF16Layout<TD, TH, TW> L;
+    constexpr int ROWH = L::ROWH, LHM = L::LHM, CHS_P = L::CHS_P, CHS_Q = L::CHS_Q;
     extern __shared__ __attribute__((aligned(16))) unsigned short smem_h[];
     unsigned short* const Ph = smem_h;               // [32][CHS_P] hi halves of the P tile
     unsigned short* const Pl = Ph + 32 * CHS_P;      // (SPLIT = 0: no lo planes -- Pl / Ql are never touched and Qh follows Ph)
@@ -275,17 +385,13 @@ __global__ __launch_bounds__(256) void wgrad_f16x3_kernel(const WgradArgs p) {
     const int sw = sidx % nstripsW; sidx /= nstripsW;
     const int thi = sidx % p.tilesH; sidx /= p.tilesH;
     const int tdi = sidx % p.tilesD; const int b = sidx / p.tilesD;
-    const int bl = p.ntab ? b % p.bper : b;
-    const float* const Pbase = p.ntab ? static_cast<const float*>(wg_tab(offsetof(WgradArgs, Ptab), b / p.bper)) : p.P;
-    const float* const Qbase = p.ntab ? static_cast<const float*>(wg_tab(offsetof(WgradArgs, Qtab), b / p.bper)) : p.Q;
+    int bl; const float* Pbase; const float* Qbase;
+    wg_batch_item(p, b, bl, Pbase, Qbase);
     const float sP = p.Pmeta ? wg_pow2_scale(amax_read(p.Pmeta)) : 1.f, sQ = p.Qmeta ? wg_pow2_scale(amax_read(p.Qmeta)) : 1.f;
     const float inv = (1.0f / sP) * (1.0f / sQ);
 
     f32x16 acc[WG_TAPS];
-#pragma unroll
-    for (int t = 0; t < WG_TAPS; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    wg_zero(acc);
 
     const int npq = (p.LW + 1) >> 1;                 // voxel pairs per Q row
     const int nQ = TD * p.LH * npq * 8;              // staging items of the Q brick: (row, pair, channel quad)
@@ -313,31 +419,13 @@ __global__ __launch_bounds__(256) void wgrad_f16x3_kernel(const WgradArgs p) {
         q_src[k] = c4 * 4; q_dst[k] = (c4 * 4) * CHS_Q + (q_d[k] * LHM + q_h[k]) * ROWH + q_w[k];
         q_ok[k] = (it < nQ) ? 1u : 0u;
     }
+    // This kernel only, on purpose: the p.dbg ablations (with pv / qv starting at 1.f, so that a run without loads still commits finite
+    // operands), the class-mode parity / qs arithmetic above, and the cross-wave hand-over through LDS at the end.
     float4 pv[PIT][2], qv[QIT][2];
 #pragma unroll
     for (int k = 0; k < PIT; ++k) pv[k][0] = pv[k][1] = make_float4(1.f, 1.f, 1.f, 1.f);
 #pragma unroll
     for (int k = 0; k < QIT; ++k) qv[k][0] = qv[k][1] = make_float4(1.f, 1.f, 1.f, 1.f);
-    // four channels of one position at ELEMENT offset `off` of a tensor of fp32 or (f16 = 1: native f16 form, channel stride % 4 == 0) fp16 elements
-    auto load4f = [&](const float* src, int nc, bool ok) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) {
-            if (nc >= 4) v = *reinterpret_cast<const float4*>(src);
-            else { if (nc > 0) v.x = src[0]; if (nc > 1) v.y = src[1]; if (nc > 2) v.z = src[2]; }
-        }
-        return v;
-    };
-    auto load4h = [&](const _Float16* src, int nc, bool ok) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) {
-            if (nc >= 4) {
-                const uint2 u = *reinterpret_cast<const uint2*>(src);
-                const wf16x2 a = __builtin_bit_cast(wf16x2, u.x), c = __builtin_bit_cast(wf16x2, u.y);
-                v = make_float4((float)a[0], (float)a[1], (float)c[0], (float)c[1]);
-            } else { if (nc > 0) v.x = (float)src[0]; if (nc > 1) v.y = (float)src[1]; if (nc > 2) v.z = (float)src[2]; }
-        }
-        return v;
-    };
     auto issue_loads = [&](int twi) {
         if (p.dbg & 1) return;
         const int p0d = tdi * TD, p0h = thi * TH, p0w = twi * TW;
@@ -347,15 +435,7 @@ __global__ __launch_bounds__(256) void wgrad_f16x3_kernel(const WgradArgs p) {
             const bool row = gd < p.Pd && gh < p.Ph;
             const size_t off = ((((size_t)bl * p.Pd + (row ? gd : 0)) * p.Ph + (row ? gh : 0)) * p.Pw + gw) * p.PCs + a0 + p_src[k];
             const int nc = p.PC - (a0 + p_src[k]);
-            if constexpr (PF16) {
-                const _Float16* src = reinterpret_cast<const _Float16*>(Pbase) + off;
-                pv[k][0] = load4h(src, nc, row && gw < p.Pw);
-                pv[k][1] = load4h(src + p.PCs, nc, row && gw + 1 < p.Pw);
-            } else {
-                const float* src = Pbase + off;
-                pv[k][0] = load4f(src, nc, row && gw < p.Pw);
-                pv[k][1] = load4f(src + p.PCs, nc, row && gw + 1 < p.Pw);
-            }
+            wg_load_pair<PF16>(pv[k], Pbase, off, p.PCs, nc, row && gw < p.Pw, row && gw + 1 < p.Pw);
         }
         const int q0d = p0d + od, q0h = p0h + ghmin, q0w = p0w + gwmin;
 #pragma unroll
@@ -364,47 +444,13 @@ __global__ __launch_bounds__(256) void wgrad_f16x3_kernel(const WgradArgs p) {
             const bool row = q_ok[k] && (unsigned)gd < (unsigned)p.Qd && (unsigned)gh < (unsigned)p.Qh;
             const size_t off = ((((size_t)bl * p.Qd + (row ? gd : 0)) * p.Qh + (row ? gh : 0)) * p.Qw + gw) * p.QCs + b0 + q_src[k];
             const int nc = p.QC - (b0 + q_src[k]);
-            if constexpr (QF16) {
-                const _Float16* src = reinterpret_cast<const _Float16*>(Qbase) + off;
-                qv[k][0] = load4h(src, nc, row && (unsigned)gw < (unsigned)p.Qw);
-                qv[k][1] = load4h(src + qs * p.QCs, nc, row && (unsigned)(gw + qs) < (unsigned)p.Qw);
-            } else {
-                const float* src = Qbase + off;
-                qv[k][0] = load4f(src, nc, row && (unsigned)gw < (unsigned)p.Qw);
-                qv[k][1] = load4f(src + qs * p.QCs, nc, row && (unsigned)(gw + qs) < (unsigned)p.Qw);
-            }
+            wg_load_pair<QF16>(qv[k], Qbase, off, qs * p.QCs, nc, row && (unsigned)gw < (unsigned)p.Qw, row && (unsigned)(gw + qs) < (unsigned)p.Qw);
         }
     };
     auto commit = [&]() {                           // registers -> scaled fp16 hi / lo pairs in LDS
         if (p.dbg & 2) return;
-#pragma unroll
-        for (int k = 0; k < PIT; ++k) {
-            const float x0[4] = {pv[k][0].x, pv[k][0].y, pv[k][0].z, pv[k][0].w}, x1[4] = {pv[k][1].x, pv[k][1].y, pv[k][1].z, pv[k][1].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if constexpr (SPLIT) {
-                    unsigned h, l;
-                    wg_split2(x0[j] * sP, x1[j] * sP, h, l);
-                    *reinterpret_cast<unsigned*>(Ph + p_dst[k] + j * CHS_P) = h;
-                    *reinterpret_cast<unsigned*>(Pl + p_dst[k] + j * CHS_P) = l;
-                } else *reinterpret_cast<unsigned*>(Ph + p_dst[k] + j * CHS_P) = wg_round2(x0[j] * sP, x1[j] * sP);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < QIT; ++k) {
-            if (q_ok[k]) {
-                const float x0[4] = {qv[k][0].x, qv[k][0].y, qv[k][0].z, qv[k][0].w}, x1[4] = {qv[k][1].x, qv[k][1].y, qv[k][1].z, qv[k][1].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (SPLIT) {
-                        unsigned h, l;
-                        wg_split2(x0[j] * sQ, x1[j] * sQ, h, l);
-                        *reinterpret_cast<unsigned*>(Qh + q_dst[k] + j * CHS_Q) = h;
-                        *reinterpret_cast<unsigned*>(Ql + q_dst[k] + j * CHS_Q) = l;
-                    } else *reinterpret_cast<unsigned*>(Qh + q_dst[k] + j * CHS_Q) = wg_round2(x0[j] * sQ, x1[j] * sQ);
-                }
-            }
-        }
+        wg_commit<SPLIT, CHS_P>(Ph, Pl, p_dst, nullptr, pv, sP);         // (every P item exists here)
+        wg_commit<SPLIT, CHS_Q>(Qh, Ql, q_dst, q_ok, qv, sQ);
     };
     const int tw_first = sw * p.strip, tw_end = ((sw + 1) * p.strip < p.tilesW) ? (sw + 1) * p.strip : p.tilesW;
     issue_loads(tw_first);
@@ -429,38 +475,7 @@ __global__ __launch_bounds__(256) void wgrad_f16x3_kernel(const WgradArgs p) {
             qoff[i] = col * CHS_Q + (pd * LHM + ph) * ROWH + ((TW == 16) ? (hb & 1) * 8 : 0);
         }
 #pragma unroll
-        for (int dh = 0; dh < 3; ++dh) {
-            if (p.g_slot[tg][dh * 3] >= 0 || p.g_slot[tg][dh * 3 + 1] >= 0 || p.g_slot[tg][dh * 3 + 2] >= 0) {
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const unsigned short* qh = Qh + qoff[i] + dh * ROWH;
-                    const unsigned short* ql = Ql + qoff[i] + dh * ROWH;
-                    const uint4 vh = *reinterpret_cast<const uint4*>(qh), vl = SPLIT ? *reinterpret_cast<const uint4*>(ql) : vh;
-                    const unsigned eh = *reinterpret_cast<const unsigned*>(qh + 8), el = SPLIT ? *reinterpret_cast<const unsigned*>(ql + 8) : eh;
-                    const wf16x8 pa_h = __builtin_bit_cast(wf16x8, ah[i]), pa_l = __builtin_bit_cast(wf16x8, al[i]);
-#pragma unroll
-                    for (int dw = 0; dw < 3; ++dw) {
-                        if (p.g_slot[tg][dh * 3 + dw] >= 0) {
-                            uint4 bh, bl;
-                            if (dw == 0) { bh = vh; bl = vl; }
-                            else if (dw == 1) {
-                                bh = make_uint4(__builtin_amdgcn_alignbit(vh.y, vh.x, 16), __builtin_amdgcn_alignbit(vh.z, vh.y, 16),
-                                                __builtin_amdgcn_alignbit(vh.w, vh.z, 16), __builtin_amdgcn_alignbit(eh, vh.w, 16));
-                                bl = make_uint4(__builtin_amdgcn_alignbit(vl.y, vl.x, 16), __builtin_amdgcn_alignbit(vl.z, vl.y, 16),
-                                                __builtin_amdgcn_alignbit(vl.w, vl.z, 16), __builtin_amdgcn_alignbit(el, vl.w, 16));
-                            } else { bh = make_uint4(vh.y, vh.z, vh.w, eh); bl = make_uint4(vl.y, vl.z, vl.w, el); }
-                            const wf16x8 qb_h = __builtin_bit_cast(wf16x8, bh), qb_l = __builtin_bit_cast(wf16x8, bl);
-                            f32x16& c = acc[dh * 3 + dw];
-                            if constexpr (SPLIT) {
-                                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_h, qb_l, c, 0, 0, 0);
-                                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_l, qb_h, c, 0, 0, 0);
-                            }
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_h, qb_h, c, 0, 0, 0);
-                        }
-                    }
-                }
-            }
-        }
+        for (int dh = 0; dh < 3; ++dh) wg_tap_row<SPLIT, 2>(acc, p, tg, dh, ah, al, Qh + dh * ROWH, Ql + dh * ROWH, qoff);     // order dh -> i -> dw
     }
     // ---- partial tiles to the workspace, slot dh * 3 + dw -> tap j of the group (records and reduce kernel of the fp32 form)
     if ((p.dbg & 8) && acc[0][0] != 12345.678f) return;
@@ -505,14 +520,11 @@ __global__ __launch_bounds__(256) void wgrad_f16x3_kernel(const WgradArgs p) {
 template <int TD, int TH, int TW, int SPLIT, int PF16, int QF16, int NA, int NB, int NG = 1>
 __global__ __launch_bounds__(64 * NA * NB * NG) void wgrad_mt_kernel(const WgradArgs p) {
     static_assert(!SPLIT || (!PF16 && !QF16), "fp16 tensors exist in the native f16 form only");
-    static_assert(TD * TH * TW == 128 && (TW == 8 || TW == 16), "128-position bricks");
     static_assert(NG == 1 || NG == 3, "tap groups per workgroup");
     constexpr int NT = 64 * NA * NB * NG;
-    constexpr int ROWH = (TW == 8) ? 16 : 24;
-    constexpr int LHM = TH + 2;
-    constexpr int CHS_P = 136;
     constexpr int TDQ = TD + (NG == 3 ? 2 : 0);        // Q planes in LDS
-    constexpr int CHS_Q = TDQ * LHM * ROWH + 8;
+    typedef WgF16Layout<TD, TH, TW, TDQ> L;
+    constexpr int ROWH = L::ROWH, LHM = L::LHM, CHS_P = L::CHS_P, CHS_Q = L::CHS_Q;
     extern __shared__ __attribute__((aligned(16))) unsigned short smem_h[];
     unsigned short* const Ph = smem_h;                              // [NA * 32][CHS_P]
     unsigned short* const Pl = Ph + NA * 32 * CHS_P;
@@ -539,7 +551,7 @@ __global__ __launch_bounds__(64 * NA * NB * NG) void wgrad_mt_kernel(const Wgrad
 
     f32x16 acc[WG_TAPS];
 #pragma unroll
-    for (int t = 0; t < WG_TAPS; ++t)
+    for (int t = 0; t < WG_TAPS; ++t)              // (spelled out: wg_zero here cost the NG = 3 kernels an s_nop and an s_waitcnt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
@@ -572,6 +584,10 @@ __global__ __launch_bounds__(64 * NA * NB * NG) void wgrad_mt_kernel(const Wgrad
         q_ok[k] = (cg < NB) ? 1u : 0u;
     }
     float4 pv[PIT][2], qv[QIT][2];
+    // This kernel only, on purpose: the brick (and its batch item) is decoded per call of issue_loads, P items can be missing (p_ok), and
+    // with NG = 3 a wave reads its Q rows wgp planes further (qoff below).
+    // The fp32 P tile of this kernel keeps its own copy of wg_load4<0>: through the shared helper every instantiation with an fp32 P tensor
+    // got two to four more register copies, and the NG = 3 f16x3 kernel ran 0.9 % slower (profiles/round9/wgrad_one_definition.md).
     auto load4f = [&](const float* src, int nc, bool ok) {
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (ok) {
@@ -580,24 +596,12 @@ __global__ __launch_bounds__(64 * NA * NB * NG) void wgrad_mt_kernel(const Wgrad
         }
         return v;
     };
-    auto load4h = [&](const _Float16* src, int nc, bool ok) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) {
-            if (nc >= 4) {
-                const uint2 u = *reinterpret_cast<const uint2*>(src);
-                const wf16x2 a = __builtin_bit_cast(wf16x2, u.x), c = __builtin_bit_cast(wf16x2, u.y);
-                v = make_float4((float)a[0], (float)a[1], (float)c[0], (float)c[1]);
-            } else { if (nc > 0) v.x = (float)src[0]; if (nc > 1) v.y = (float)src[1]; if (nc > 2) v.z = (float)src[2]; }
-        }
-        return v;
-    };
     auto issue_loads = [&](int bi) {
         const int twi = bi % p.tilesW; int t = bi / p.tilesW;
         const int thi = t % p.tilesH; t /= p.tilesH;
         const int tdi = t % p.tilesD; const int b = t / p.tilesD;
-        const int bl = p.ntab ? b % p.bper : b;
-        const float* const Pbase = p.ntab ? static_cast<const float*>(wg_tab(offsetof(WgradArgs, Ptab), b / p.bper)) : p.P;
-        const float* const Qbase = p.ntab ? static_cast<const float*>(wg_tab(offsetof(WgradArgs, Qtab), b / p.bper)) : p.Q;
+        int bl; const float* Pbase; const float* Qbase;
+        wg_batch_item(p, b, bl, Pbase, Qbase);
         const int p0d = tdi * TD, p0h = thi * TH, p0w = twi * TW;
 #pragma unroll
         for (int k = 0; k < PIT; ++k) {
@@ -605,11 +609,8 @@ __global__ __launch_bounds__(64 * NA * NB * NG) void wgrad_mt_kernel(const Wgrad
             const bool row = p_ok[k] && gd < p.Pd && gh < p.Ph;
             const size_t off = ((((size_t)bl * p.Pd + (row ? gd : 0)) * p.Ph + (row ? gh : 0)) * p.Pw + gw) * p.PCs + a0 + p_src[k];
             const int nc = p.PC - (a0 + p_src[k]);
-            if constexpr (PF16) {
-                const _Float16* src = reinterpret_cast<const _Float16*>(Pbase) + off;
-                pv[k][0] = load4h(src, nc, row && gw < p.Pw);
-                pv[k][1] = load4h(src + p.PCs, nc, row && gw + 1 < p.Pw);
-            } else {
+            if constexpr (PF16) wg_load_pair<1>(pv[k], Pbase, off, p.PCs, nc, row && gw < p.Pw, row && gw + 1 < p.Pw);
+            else {
                 const float* src = Pbase + off;
                 pv[k][0] = load4f(src, nc, row && gw < p.Pw);
                 pv[k][1] = load4f(src + p.PCs, nc, row && gw + 1 < p.Pw);
@@ -622,47 +623,12 @@ __global__ __launch_bounds__(64 * NA * NB * NG) void wgrad_mt_kernel(const Wgrad
             const bool row = q_ok[k] && (unsigned)gd < (unsigned)p.Qd && (unsigned)gh < (unsigned)p.Qh;
             const size_t off = ((((size_t)bl * p.Qd + (row ? gd : 0)) * p.Qh + (row ? gh : 0)) * p.Qw + gw) * p.QCs + b0 + q_src[k];
             const int nc = p.QC - (b0 + q_src[k]);
-            if constexpr (QF16) {
-                const _Float16* src = reinterpret_cast<const _Float16*>(Qbase) + off;
-                qv[k][0] = load4h(src, nc, row && (unsigned)gw < (unsigned)p.Qw);
-                qv[k][1] = load4h(src + p.QCs, nc, row && (unsigned)(gw + 1) < (unsigned)p.Qw);
-            } else {
-                const float* src = Qbase + off;
-                qv[k][0] = load4f(src, nc, row && (unsigned)gw < (unsigned)p.Qw);
-                qv[k][1] = load4f(src + p.QCs, nc, row && (unsigned)(gw + 1) < (unsigned)p.Qw);
-            }
+            wg_load_pair<QF16>(qv[k], Qbase, off, p.QCs, nc, row && (unsigned)gw < (unsigned)p.Qw, row && (unsigned)(gw + 1) < (unsigned)p.Qw);
         }
     };
     auto commit = [&]() {
-#pragma unroll
-        for (int k = 0; k < PIT; ++k) {
-            if (!p_ok[k]) continue;
-            const float x0[4] = {pv[k][0].x, pv[k][0].y, pv[k][0].z, pv[k][0].w}, x1[4] = {pv[k][1].x, pv[k][1].y, pv[k][1].z, pv[k][1].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if constexpr (SPLIT) {
-                    unsigned h, l;
-                    wg_split2(x0[j] * sP, x1[j] * sP, h, l);
-                    *reinterpret_cast<unsigned*>(Ph + p_dst[k] + j * CHS_P) = h;
-                    *reinterpret_cast<unsigned*>(Pl + p_dst[k] + j * CHS_P) = l;
-                } else *reinterpret_cast<unsigned*>(Ph + p_dst[k] + j * CHS_P) = wg_round2(x0[j] * sP, x1[j] * sP);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < QIT; ++k) {
-            if (q_ok[k]) {
-                const float x0[4] = {qv[k][0].x, qv[k][0].y, qv[k][0].z, qv[k][0].w}, x1[4] = {qv[k][1].x, qv[k][1].y, qv[k][1].z, qv[k][1].w};
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (SPLIT) {
-                        unsigned h, l;
-                        wg_split2(x0[j] * sQ, x1[j] * sQ, h, l);
-                        *reinterpret_cast<unsigned*>(Qh + q_dst[k] + j * CHS_Q) = h;
-                        *reinterpret_cast<unsigned*>(Ql + q_dst[k] + j * CHS_Q) = l;
-                    } else *reinterpret_cast<unsigned*>(Qh + q_dst[k] + j * CHS_Q) = wg_round2(x0[j] * sQ, x1[j] * sQ);
-                }
-            }
-        }
+        wg_commit<SPLIT, CHS_P>(Ph, Pl, p_dst, p_ok, pv, sP);
+        wg_commit<SPLIT, CHS_Q>(Qh, Ql, q_dst, q_ok, qv, sQ);
     };
     if (bi0 < bi1) issue_loads(bi0);
     const unsigned short* const Pa_h = Ph + (wa * 32 + col) * CHS_P;
@@ -679,39 +645,11 @@ __global__ __launch_bounds__(64 * NA * NB * NG) void wgrad_mt_kernel(const Wgrad
             const uint4 ah = *reinterpret_cast<const uint4*>(Pa_h + hb * 8);
             uint4 al = ah;
             if constexpr (SPLIT) al = *reinterpret_cast<const uint4*>(Pa_l + hb * 8);
-            const wf16x8 pa_h = __builtin_bit_cast(wf16x8, ah), pa_l = __builtin_bit_cast(wf16x8, al);
             const int prow = (TW == 8) ? hb : (hb >> 1);
             const int pd = prow / TH, ph = prow % TH;
             const int qoff = qcol + ((pd + (NG == 3 ? wgp : 0)) * LHM + ph) * ROWH + ((TW == 16) ? (hb & 1) * 8 : 0);
 #pragma unroll
-            for (int dh = 0; dh < 3; ++dh) {
-                if (p.g_slot[tg][dh * 3] >= 0 || p.g_slot[tg][dh * 3 + 1] >= 0 || p.g_slot[tg][dh * 3 + 2] >= 0) {
-                    const unsigned short* qh = Qh + qoff + dh * ROWH;
-                    const unsigned short* ql = Ql + qoff + dh * ROWH;
-                    const uint4 vh = *reinterpret_cast<const uint4*>(qh), vl = SPLIT ? *reinterpret_cast<const uint4*>(ql) : vh;
-                    const unsigned eh = *reinterpret_cast<const unsigned*>(qh + 8), el = SPLIT ? *reinterpret_cast<const unsigned*>(ql + 8) : eh;
-#pragma unroll
-                    for (int dw = 0; dw < 3; ++dw) {
-                        if (p.g_slot[tg][dh * 3 + dw] >= 0) {
-                            uint4 bh, bl;
-                            if (dw == 0) { bh = vh; bl = vl; }
-                            else if (dw == 1) {
-                                bh = make_uint4(__builtin_amdgcn_alignbit(vh.y, vh.x, 16), __builtin_amdgcn_alignbit(vh.z, vh.y, 16),
-                                                __builtin_amdgcn_alignbit(vh.w, vh.z, 16), __builtin_amdgcn_alignbit(eh, vh.w, 16));
-                                bl = make_uint4(__builtin_amdgcn_alignbit(vl.y, vl.x, 16), __builtin_amdgcn_alignbit(vl.z, vl.y, 16),
-                                                __builtin_amdgcn_alignbit(vl.w, vl.z, 16), __builtin_amdgcn_alignbit(el, vl.w, 16));
-                            } else { bh = make_uint4(vh.y, vh.z, vh.w, eh); bl = make_uint4(vl.y, vl.z, vl.w, el); }
-                            const wf16x8 qb_h = __builtin_bit_cast(wf16x8, bh), qb_l = __builtin_bit_cast(wf16x8, bl);
-                            f32x16& c = acc[dh * 3 + dw];
-                            if constexpr (SPLIT) {
-                                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_h, qb_l, c, 0, 0, 0);
-                                c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_l, qb_h, c, 0, 0, 0);
-                            }
-                            c = __builtin_amdgcn_mfma_f32_32x32x16_f16(pa_h, qb_h, c, 0, 0, 0);
-                        }
-                    }
-                }
-            }
+            for (int dh = 0; dh < 3; ++dh) wg_tap_row<SPLIT, 1>(acc, p, tg, dh, &ah, &al, Qh + dh * ROWH, Ql + dh * ROWH, &qoff);         // order kb -> dh -> dw
         }
     }
     // ---- this wave's tile record, slot dh * 3 + dw -> tap j of the group
@@ -773,364 +711,357 @@ using namespace osa;
 static int g_wgrad_mt = 1;
 namespace osa { void wgrad_set_multi_tile(int on) { g_wgrad_mt = on ? 1 : 0; } }
 
+// One call of any entry point below.
 // conv:   P = dy [B,Do,Ho,Wo,Co]  Q = x  [B,Di,Hi,Wi,Ci]  dW [Co][Ci][k]   (transposed = 0)
 // deconv: P = x  [B,Di,Hi,Wi,Ci]  Q = dy [B,Do,Ho,Wo,Co]  dW [Ci][Co][k]   (transposed = 1, stride 2, off = t - pad)
-// query != nullptr: only compute the workspace size of the two-stage form for these dimensions (no pointer is touched)
-static int wgrad_impl(const float* x, const float* dy, float* dw,
-                      int B, int Di, int Hi, int Wi, int Ci, int xCs,
-                      int Do, int Ho, int Wo, int Co, int dyCs,
-                      int kd, int kh, int kw, int stride,
-                      int pad_d, int pad_h, int pad_w, int dil_d, int dil_h, int dil_w,
-                      int transposed, float* ws, size_t ws_bytes, size_t* query, void* stream,
-                      int f16x3 = 0, const float* x_meta = nullptr, const float* dy_meta = nullptr, int x_f16 = 0, int dy_f16 = 0,
-                      const void* const* x_tab = nullptr, const void* const* dy_tab = nullptr, int n_tab = 0) {
-    if (!query) OSA_REQUIRE(x && dy && dw, "conv3d_wgrad: NULL pointer");
-    if (x_f16 || dy_f16) OSA_REQUIRE(f16x3 == 2, "conv3d_wgrad: fp16 tensors exist in the native f16 form only");
+struct WgradDims {                // in the order of the entry points' parameters (xCs / dyCs: 4 in the queries, which pass no strides)
+    int B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs;
+    int kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed;
+};
+struct WgradProblem {
+    WgradDims d;
+    int form = 0;                                          // 0: exact fp32 kernel, 1: f16x3, 2: native f16
+    const void* x = nullptr; const void* dy = nullptr; float* dw = nullptr;
+    const float* x_meta = nullptr; const float* dy_meta = nullptr;      // range blocks (forms 1 and 2)
+    int x_f16 = 0, dy_f16 = 0;                             // form 2: the tensor holds fp16 elements
+    const void* const* x_tab = nullptr; const void* const* dy_tab = nullptr; int n_tab = 0;     // a LIST of n_tab equally shaped tensors
+    float* ws = nullptr; size_t ws_bytes = 0;              // two-stage form; NULL (form 0 only): float atomics
+    size_t* query = nullptr;                               // only compute the workspace size of the two-stage form (no pointer is touched)
+    void* stream = nullptr;
+};
+struct WgOffsets { int dmax, hmax, wmax; };                // largest tap offsets (the smallest are a.dmin / hmin / wmin)
+
+// validation, P / Q roles, the tap table and, for stride 2, the class decomposition
+static int wgrad_setup(const WgradProblem& q, WgradArgs& a, WgOffsets& o) {
+    const WgradDims& d = q.d;
+    const int transposed = d.transposed, kd = d.kd, kh = d.kh, kw = d.kw;
+    if (!q.query) OSA_REQUIRE(q.x && q.dy && q.dw, "conv3d_wgrad: NULL pointer");
+    if (q.x_f16 || q.dy_f16) OSA_REQUIRE(q.form == 2, "conv3d_wgrad: fp16 tensors exist in the native f16 form only");
     const int T = kd * kh * kw;
     OSA_REQUIRE(T >= 1 && T <= 64, "conv3d_wgrad: %d taps unsupported", T);
-    OSA_REQUIRE(stride == 1 || stride == 2, "conv3d_wgrad: stride %d unsupported", stride);
-    if (!query) OSA_REQUIRE(xCs % 4 == 0 && dyCs % 4 == 0 && ((size_t)x & (x_f16 ? 7 : 15)) == 0 && ((size_t)dy & (dy_f16 ? 7 : 15)) == 0,
-                            "conv3d_wgrad: tensors must be 16-byte (fp16: 8-byte) aligned with voxel strides %% 4 == 0");
-    WgradArgs a;
+    OSA_REQUIRE(d.stride == 1 || d.stride == 2, "conv3d_wgrad: stride %d unsupported", d.stride);
+    if (!q.query) OSA_REQUIRE(d.xCs % 4 == 0 && d.dyCs % 4 == 0 && ((size_t)q.x & (q.x_f16 ? 7 : 15)) == 0 && ((size_t)q.dy & (q.dy_f16 ? 7 : 15)) == 0,
+                              "conv3d_wgrad: tensors must be 16-byte (fp16: 8-byte) aligned with voxel strides %% 4 == 0");
     memset(&a, 0, sizeof(a));
-    a.B = B; a.T = T; a.kh = kh; a.kw = kw; a.kvol = T;
-    a.s = (transposed ? 2 : stride);
-    const int sd = (!transposed && Di == 1 && kd == 1) ? 1 : a.s;
+    a.B = d.B; a.T = T; a.kh = kh; a.kw = kw; a.kvol = T;
+    a.s = (transposed ? 2 : d.stride);
+    const int sd = (!transposed && d.Di == 1 && kd == 1) ? 1 : a.s;
     OSA_REQUIRE(sd == a.s, "conv3d_wgrad: flat (D=1) strided layers are not supported yet");
+    const float* const x = static_cast<const float*>(q.x); const float* const dy = static_cast<const float*>(q.dy);
     if (!transposed) {
-        a.P = dy; a.Pd = Do; a.Ph = Ho; a.Pw = Wo; a.PC = Co; a.PCs = dyCs;
-        a.Q = x; a.Qd = Di; a.Qh = Hi; a.Qw = Wi; a.QC = Ci; a.QCs = xCs;
-        a.A = Co; a.Bc = Ci;
+        a.P = dy; a.Pd = d.Do; a.Ph = d.Ho; a.Pw = d.Wo; a.PC = d.Co; a.PCs = d.dyCs;
+        a.Q = x; a.Qd = d.Di; a.Qh = d.Hi; a.Qw = d.Wi; a.QC = d.Ci; a.QCs = d.xCs;
+        a.A = d.Co; a.Bc = d.Ci;
     } else {
-        OSA_REQUIRE(stride == 2, "conv3d_wgrad: transposed convs are stride 2");
-        a.P = x; a.Pd = Di; a.Ph = Hi; a.Pw = Wi; a.PC = Ci; a.PCs = xCs;
-        a.Q = dy; a.Qd = Do; a.Qh = Ho; a.Qw = Wo; a.QC = Co; a.QCs = dyCs;
-        a.A = Ci; a.Bc = Co;
+        OSA_REQUIRE(d.stride == 2, "conv3d_wgrad: transposed convs are stride 2");
+        a.P = x; a.Pd = d.Di; a.Ph = d.Hi; a.Pw = d.Wi; a.PC = d.Ci; a.PCs = d.xCs;
+        a.Q = dy; a.Qd = d.Do; a.Qh = d.Ho; a.Qw = d.Wo; a.QC = d.Co; a.QCs = d.dyCs;
+        a.A = d.Ci; a.Bc = d.Co;
     }
-    a.dW = dw;
-    if (n_tab > 0) {
-        OSA_REQUIRE(n_tab <= 24 && B % n_tab == 0 && x_tab && dy_tab, "conv3d_wgrad: a tensor list holds at most 24 equally shaped items (got %d, batch %d)", n_tab, B);
-        a.ntab = n_tab; a.bper = B / n_tab;
-        for (int i = 0; i < n_tab; ++i) {
-            OSA_REQUIRE(x_tab[i] && dy_tab[i] && ((size_t)x_tab[i] & (x_f16 ? 7 : 15)) == 0 && ((size_t)dy_tab[i] & (dy_f16 ? 7 : 15)) == 0, "conv3d_wgrad: list item %d NULL or misaligned", i);
-            a.Ptab[i] = transposed ? x_tab[i] : dy_tab[i];
-            a.Qtab[i] = transposed ? dy_tab[i] : x_tab[i];
+    if (q.form) {                 // (the fp32 kernel reads neither)
+        a.Pmeta = transposed ? q.x_meta : q.dy_meta; a.Qmeta = transposed ? q.dy_meta : q.x_meta;
+        a.Pf16 = transposed ? q.x_f16 : q.dy_f16; a.Qf16 = transposed ? q.dy_f16 : q.x_f16;
+    }
+    a.dW = q.dw;
+    if (q.n_tab > 0) {
+        OSA_REQUIRE(q.n_tab <= 24 && d.B % q.n_tab == 0 && q.x_tab && q.dy_tab, "conv3d_wgrad: a tensor list holds at most 24 equally shaped items (got %d, batch %d)", q.n_tab, d.B);
+        a.ntab = q.n_tab; a.bper = d.B / q.n_tab;
+        for (int i = 0; i < q.n_tab; ++i) {
+            OSA_REQUIRE(q.x_tab[i] && q.dy_tab[i] && ((size_t)q.x_tab[i] & (q.x_f16 ? 7 : 15)) == 0 && ((size_t)q.dy_tab[i] & (q.dy_f16 ? 7 : 15)) == 0, "conv3d_wgrad: list item %d NULL or misaligned", i);
+            a.Ptab[i] = transposed ? q.x_tab[i] : q.dy_tab[i];
+            a.Qtab[i] = transposed ? q.dy_tab[i] : q.x_tab[i];
         }
     }
-    int t = 0, dmax = -128, hmax = -128, wmax = -128;
+    int t = 0;
+    o.dmax = o.hmax = o.wmax = -128;
     a.dmin = a.hmin = a.wmin = 127;
     for (int z = 0; z < kd; ++z) for (int y = 0; y < kh; ++y) for (int xx = 0; xx < kw; ++xx, ++t) {
-        const int od = transposed ? z - pad_d : z * dil_d - pad_d;
-        const int oh = transposed ? y - pad_h : y * dil_h - pad_h;
-        const int ow = transposed ? xx - pad_w : xx * dil_w - pad_w;
+        const int od = transposed ? z - d.pad_d : z * d.dil_d - d.pad_d;
+        const int oh = transposed ? y - d.pad_h : y * d.dil_h - d.pad_h;
+        const int ow = transposed ? xx - d.pad_w : xx * d.dil_w - d.pad_w;
         a.od[t] = (signed char)od; a.oh[t] = (signed char)oh; a.ow[t] = (signed char)ow;
-        a.dmin = od < a.dmin ? od : a.dmin; dmax = od > dmax ? od : dmax;
-        a.hmin = oh < a.hmin ? oh : a.hmin; hmax = oh > hmax ? oh : hmax;
-        a.wmin = ow < a.wmin ? ow : a.wmin; wmax = ow > wmax ? ow : wmax;
+        a.dmin = od < a.dmin ? od : a.dmin; o.dmax = od > o.dmax ? od : o.dmax;
+        a.hmin = oh < a.hmin ? oh : a.hmin; o.hmax = oh > o.hmax ? oh : o.hmax;
+        a.wmin = ow < a.wmin ? ow : a.wmin; o.wmax = ow > o.wmax ? ow : o.wmax;
     }
     a.tgroups = cdiv(T, WG_TAPS);
-    if (a.s == 2) {
-        // class-major tap list (transposed convs AND stride-2 convs: both read Q at 2*pos + off): for parity (pd, ph, pw) every kernel
-        // index whose offset has that parity; delta = floor(off / 2)
-        a.cls = 1;
-        int n = 0;
-        for (int c = 0; c < 8; ++c) {
-            const int par[3] = {(c >> 2) & 1, (c >> 1) & 1, c & 1};
-            const int kk[3] = {kd, kh, kw}, pd3[3] = {pad_d, pad_h, pad_w}, dl3[3] = {transposed ? 1 : dil_d, transposed ? 1 : dil_h, transposed ? 1 : dil_w};
-            int idx[3][4], del[3][4], cnt[3];
-            for (int dim = 0; dim < 3; ++dim) {
-                cnt[dim] = 0;
-                for (int k = 0; k < kk[dim]; ++k) {
-                    const int off = k * dl3[dim] - pd3[dim];
-                    if (((off % 2) + 2) % 2 != par[dim]) continue;
-                    idx[dim][cnt[dim]] = k; del[dim][cnt[dim]] = (off - par[dim]) / 2; ++cnt[dim];      // off - par is even
-                }
-                for (int i = 0; i < cnt[dim]; ++i)
-                    OSA_REQUIRE(del[dim][i] == -par[dim] || del[dim][i] == 1 - par[dim], "conv3d_wgrad: transposed kernel %d / pad %d out of the supported range", kk[dim], pd3[dim]);
+    if (a.s != 2) return 0;
+    // class-major tap list (transposed convs AND stride-2 convs: both read Q at 2*pos + off): for parity (pd, ph, pw) every kernel
+    // index whose offset has that parity; delta = floor(off / 2)
+    a.cls = 1;
+    int n = 0;
+    for (int c = 0; c < 8; ++c) {
+        const int par[3] = {(c >> 2) & 1, (c >> 1) & 1, c & 1};
+        const int kk[3] = {kd, kh, kw}, pd3[3] = {d.pad_d, d.pad_h, d.pad_w}, dl3[3] = {transposed ? 1 : d.dil_d, transposed ? 1 : d.dil_h, transposed ? 1 : d.dil_w};
+        int idx[3][4], del[3][4], cnt[3];
+        for (int dim = 0; dim < 3; ++dim) {
+            cnt[dim] = 0;
+            for (int k = 0; k < kk[dim]; ++k) {
+                const int off = k * dl3[dim] - pd3[dim];
+                if (((off % 2) + 2) % 2 != par[dim]) continue;
+                // off - par is even.  Checked before the entry is written: only the deltas -par and 1 - par are in range, so idx / del never
+                // hold more than two entries (a 9 x 1 x 1 kernel at pad 0 has five indices of parity 0)
+                OSA_REQUIRE((off - par[dim]) / 2 == -par[dim] || (off - par[dim]) / 2 == 1 - par[dim], "conv3d_wgrad: transposed kernel %d / pad %d out of the supported range", kk[dim], pd3[dim]);
+                idx[dim][cnt[dim]] = k; del[dim][cnt[dim]] = (off - par[dim]) / 2; ++cnt[dim];
             }
-            a.g_t0[c] = (signed char)n; a.g_par[c] = (signed char)c;
-            for (int i = 0; i < cnt[0]; ++i) for (int j = 0; j < cnt[1]; ++j) for (int l = 0; l < cnt[2]; ++l, ++n) {
-                a.od[n] = (signed char)del[0][i]; a.oh[n] = (signed char)del[1][j]; a.ow[n] = (signed char)del[2][l];
-                a.tapid[n] = (signed char)((idx[0][i] * kh + idx[1][j]) * kw + idx[2][l]);
-            }
-            a.g_nt[c] = (signed char)(n - a.g_t0[c]);
-            OSA_REQUIRE(a.g_nt[c] <= WG_TAPS, "conv3d_wgrad: %d taps in one parity class", (int)a.g_nt[c]);
         }
-        OSA_REQUIRE(n == T, "conv3d_wgrad: class decomposition covers %d of %d taps", n, T);
-        a.tgroups = 8;
+        a.g_t0[c] = (signed char)n; a.g_par[c] = (signed char)c;
+        for (int i = 0; i < cnt[0]; ++i) for (int j = 0; j < cnt[1]; ++j) for (int l = 0; l < cnt[2]; ++l, ++n) {
+            a.od[n] = (signed char)del[0][i]; a.oh[n] = (signed char)del[1][j]; a.ow[n] = (signed char)del[2][l];
+            a.tapid[n] = (signed char)((idx[0][i] * kh + idx[1][j]) * kw + idx[2][l]);
+        }
+        a.g_nt[c] = (signed char)(n - a.g_t0[c]);
+        OSA_REQUIRE(a.g_nt[c] <= WG_TAPS, "conv3d_wgrad: %d taps in one parity class", (int)a.g_nt[c]);
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (f16x3) {
-        // split-precision form (wgrad_f16x3_kernel): unit dilation; unit stride with <= 3x3 planes, or the stride-2 / transposed layers in
-        // class mode (the parity classes built above).  A tap group = the taps of one d offset (of one class).  Not eligible -> *query = 0 /
-        // error: the caller keeps the fp32 form.
-        bool ok = dil_d == 1 && dil_h == 1 && dil_w == 1;
-        if (a.s == 1) ok = ok && !transposed && kh <= 3 && kw <= 3;
-        if (query && !ok) { *query = 0; return 0; }
-        OSA_REQUIRE(ok, "conv3d_wgrad_f16x3: layer not eligible (unit dilation; unit-stride layers: kh, kw <= 3)");
-        const bool flat16 = (a.Pd == 1 && kd == 1);
-        const int TD = flat16 ? 1 : 2, TH = 8, TW = flat16 ? 16 : 8;
-        int ng = 0;
-        memset(a.g_slot, -1, sizeof(a.g_slot));
-        if (a.cls) {
-            // split every class's (d-major) tap run by its d delta
-            signed char c_t0[8], c_nt[8];
-            memcpy(c_t0, a.g_t0, 8); memcpy(c_nt, a.g_nt, 8);
-            for (int c = 0; c < 8; ++c) {
-                const int parh = (c >> 1) & 1, parw = c & 1;
-                int i = c_t0[c];
-                const int e = c_t0[c] + c_nt[c];
-                while (i < e) {
-                    int j = i;
-                    while (j < e && a.od[j] == a.od[i]) ++j;
-                    OSA_REQUIRE(ng < 16, "conv3d_wgrad_f16x3: more than 16 tap groups");
-                    a.g_t0[ng] = (signed char)i; a.g_nt[ng] = (signed char)(j - i); a.g_par[ng] = (signed char)c; a.g_od[ng] = a.od[i];
-                    for (int t2 = i; t2 < j; ++t2) {
-                        const int dh = a.oh[t2] + parh, dw = a.ow[t2] + parw;            // delta - (-par) in {0, 1}
-                        OSA_REQUIRE(dh >= 0 && dh <= 2 && dw >= 0 && dw <= 2 && a.g_slot[ng][dh * 3 + dw] < 0, "conv3d_wgrad_f16x3: tap offsets out of range");
-                        a.g_slot[ng][dh * 3 + dw] = (signed char)(t2 - i);
-                    }
-                    ++ng; i = j;
+    OSA_REQUIRE(n == T, "conv3d_wgrad: class decomposition covers %d of %d taps", n, T);
+    a.tgroups = 8;
+    return 0;
+}
+
+// f16 family (wgrad_f16x3_kernel / wgrad_mt_kernel): a tap group = the taps of ONE d offset (of one parity class in class mode), its taps in
+// the 3 x 3 accumulator slots dh * 3 + dw; position bricks of 128 positions and the Q brick's rows
+static int wgrad_f16_groups(WgradArgs& a, const WgOffsets& o, int kd, bool flat16) {
+    const int kh = a.kh, kw = a.kw;
+    const int TD = flat16 ? 1 : 2, TH = 8, TW = flat16 ? 16 : 8;
+    int ng = 0;
+    memset(a.g_slot, -1, sizeof(a.g_slot));
+    if (a.cls) {
+        // split every class's (d-major) tap run by its d delta
+        signed char c_t0[8], c_nt[8];
+        memcpy(c_t0, a.g_t0, 8); memcpy(c_nt, a.g_nt, 8);
+        for (int c = 0; c < 8; ++c) {
+            const int parh = (c >> 1) & 1, parw = c & 1;
+            int i = c_t0[c];
+            const int e = c_t0[c] + c_nt[c];
+            while (i < e) {
+                int j = i;
+                while (j < e && a.od[j] == a.od[i]) ++j;
+                OSA_REQUIRE(ng < 16, "conv3d_wgrad_f16x3: more than 16 tap groups");
+                a.g_t0[ng] = (signed char)i; a.g_nt[ng] = (signed char)(j - i); a.g_par[ng] = (signed char)c; a.g_od[ng] = a.od[i];
+                for (int t2 = i; t2 < j; ++t2) {
+                    const int dh = a.oh[t2] + parh, dw = a.ow[t2] + parw;            // delta - (-par) in {0, 1}
+                    OSA_REQUIRE(dh >= 0 && dh <= 2 && dw >= 0 && dw <= 2 && a.g_slot[ng][dh * 3 + dw] < 0, "conv3d_wgrad_f16x3: tap offsets out of range");
+                    a.g_slot[ng][dh * 3 + dw] = (signed char)(t2 - i);
                 }
+                ++ng; i = j;
             }
-            a.LH = TH + 1; a.LW = TW + 1;
-        } else {
-            // taps are (z, y, x)-major: group = one z
-            const int khw = kh * kw;
-            for (int z = 0; z < kd; ++z) {
-                a.g_t0[ng] = (signed char)(z * khw); a.g_nt[ng] = (signed char)khw; a.g_par[ng] = 0; a.g_od[ng] = a.od[z * khw];
-                for (int y = 0; y < kh; ++y) for (int xx = 0; xx < kw; ++xx) a.g_slot[ng][y * 3 + xx] = (signed char)(y * kw + xx);
-                ++ng;
-            }
-            a.LH = TH + (hmax - a.hmin); a.LW = TW + (wmax - a.wmin);
         }
-        a.LD = TD;
-        a.tgroups = ng;
-        a.tilesD = cdiv(a.Pd, TD); a.tilesH = cdiv(a.Ph, TH); a.tilesW = cdiv(a.Pw, TW);
-        const int chs_q = TD * (TH + 2) * (flat16 ? 24 : 16) + 8;
-        const int planes = (f16x3 == 2) ? 1 : 2;              // hi (+ lo) planes of P and Q
-        const size_t lds_ops = (size_t)(planes * 32 * 136 + planes * 32 * chs_q) * sizeof(unsigned short);
-        const size_t lds = lds_ops > (size_t)3 * 16 * 64 * sizeof(float) ? lds_ops : (size_t)3 * 16 * 64 * sizeof(float);   // (the hand-over of the partial tiles reuses it: 3 waves x 16 x 64 floats)
-        const int gy = cdiv(a.A, 32) * cdiv(a.Bc, 32);
-        if (!a.cls && g_wgrad_mt && !flat16 && kd == 3 && a.tgroups == 3 && cdiv(a.A, 32) * cdiv(a.Bc, 32) == 1 &&
-            a.g_od[0] == a.dmin && a.g_od[1] == a.dmin + 1 && a.g_od[2] == a.dmin + 2) {
-            // few channel tiles, 3 x 3 x 3 taps: ONE workgroup per (tiles, brick range) with the three kd planes as three groups of waves (NG = 3)
-            const int atl = cdiv(a.A, 32), btl = cdiv(a.Bc, 32);
-            const int NA = 1, NB = 1;                                       // (two-tile layers spill at 6 waves / 256 registers: they keep the single-tile kernel)
-            const long long nbricks = (long long)B * a.tilesD * a.tilesH * a.tilesW;
-            OSA_REQUIRE(nbricks < (1ll << 30), "conv3d_wgrad_f16x3: too many position bricks");
-            long long nstr = 2 * 256ll;
-            if (nstr > cdiv((int)nbricks, 4)) nstr = cdiv((int)nbricks, 4);
-            if (nstr < 1) nstr = 1;
-            a.strip = exp_int("OSA_WGRAD_STRIP", (int)cdiv((int)nbricks, (int)nstr));
-            if (a.strip < 1) a.strip = 1;
-            nstr = cdiv((int)nbricks, a.strip);
-            const long long gx = nstr * 3;
-            const size_t need = (size_t)gx * gy * WG_TAPS * 1024 * sizeof(float);
-            if (query) { *query = need; return 0; }
-            OSA_REQUIRE(ws && ws_bytes >= need && ((size_t)ws & 15) == 0, "conv3d_wgrad_f16x3: workspace of %zu B needed (got %zu)", need, ws_bytes);
-            if (f16x3 == 1) OSA_REQUIRE(x_meta && dy_meta, "conv3d_wgrad_f16x3: range blocks of x and dy required");
-            a.ws = ws;
-            a.Pmeta = dy_meta; a.Qmeta = x_meta;
-            a.Pf16 = dy_f16; a.Qf16 = x_f16;
-            const int chs_q3 = (TD + 2) * (TH + 2) * 16 + 8;
-            const size_t lds_mt = (size_t)planes * (NA * 32 * 136 + NB * 32 * chs_q3) * sizeof(unsigned short);
-            OSA_REQUIRE(lds_mt <= 160 * 1024, "conv3d_wgrad_f16x3: %zu B of LDS", lds_mt);
-            dim3 grid((unsigned)nstr, 1), block(64 * NA * NB * 3);
-#define OSA_WG_G3_LAUNCH(...)                                                                                                         \
-            do { (void)hipFuncSetAttribute((const void*)wgrad_mt_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt); \
-                 hipLaunchKernelGGL((wgrad_mt_kernel<__VA_ARGS__>), grid, block, lds_mt, st, a); } while (0)
-#define OSA_WG_G3_T(NA_, NB_)                                                                                                         \
-            if (f16x3 == 1) OSA_WG_G3_LAUNCH(2, 8, 8, 1, 0, 0, NA_, NB_, 3);                                                           \
-            else switch (a.Pf16 * 2 + a.Qf16) {                                                                                       \
-                case 0: OSA_WG_G3_LAUNCH(2, 8, 8, 0, 0, 0, NA_, NB_, 3); break;                                                       \
-                case 1: OSA_WG_G3_LAUNCH(2, 8, 8, 0, 0, 1, NA_, NB_, 3); break;                                                       \
-                case 2: OSA_WG_G3_LAUNCH(2, 8, 8, 0, 1, 0, NA_, NB_, 3); break;                                                       \
-                default: OSA_WG_G3_LAUNCH(2, 8, 8, 0, 1, 1, NA_, NB_, 3); break;                                                      \
-            }
-            OSA_WG_G3_T(1, 1)
-#undef OSA_WG_G3_T
-#undef OSA_WG_G3_LAUNCH
-            OSA_LAUNCH_CHECK("conv3d_wgrad_mt_g3");
-            WgradReduceArgs r;
-            memset(&r, 0, sizeof(r));
-            r.ws = ws; r.dW = dw; r.gx = (int)gx; r.tgroups = 3; r.nstrips = (int)nstr;
-            r.A = a.A; r.Bc = a.Bc; r.kvol = T; r.atiles = atl; r.T = T;
-            r.cls = 1;
-            for (int t2 = 0; t2 < T; ++t2) r.tapid[t2] = (signed char)t2;
-            memcpy(r.g_t0, a.g_t0, sizeof(r.g_t0)); memcpy(r.g_nt, a.g_nt, sizeof(r.g_nt));
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(WG_TAPS * 1024 / 256, 3, gy), dim3(256), 0, st, r);
-            OSA_LAUNCH_CHECK("conv3d_wgrad_mt_g3_reduce");
-            return 0;
+        a.LH = TH + 1; a.LW = TW + 1;
+    } else {
+        // taps are (z, y, x)-major: group = one z
+        const int khw = kh * kw;
+        for (int z = 0; z < kd; ++z) {
+            OSA_REQUIRE(ng < 16, "conv3d_wgrad_f16x3: more than 16 tap groups");
+            a.g_t0[ng] = (signed char)(z * khw); a.g_nt[ng] = (signed char)khw; a.g_par[ng] = 0; a.g_od[ng] = a.od[z * khw];
+            for (int y = 0; y < kh; ++y) for (int xx = 0; xx < kw; ++xx) a.g_slot[ng][y * 3 + xx] = (signed char)(y * kw + xx);
+            ++ng;
         }
-        if (!a.cls && g_wgrad_mt && cdiv(a.A, 32) * cdiv(a.Bc, 32) >= 4) {
-            // multi-tile form (wgrad_mt_kernel): NA x NB tiles per workgroup, a contiguous range of `strip` bricks per workgroup
-            const int atl = cdiv(a.A, 32), btl = cdiv(a.Bc, 32);
-            const int NA = (atl >= 3) ? 4 : 2, NB = 2;
-            const int gyb = cdiv(atl, NA) * cdiv(btl, NB);
-            const long long nbricks = (long long)B * a.tilesD * a.tilesH * a.tilesW;
-            OSA_REQUIRE(nbricks < (1ll << 30), "conv3d_wgrad_f16x3: too many position bricks");
-            // ~2 workgroups per CU over the whole launch, at least 4 bricks each (a hand-over is a 36 KB record per wave)
-            long long nstr = (2 * 256ll) / ((long long)gyb * a.tgroups);
-            if (nstr < 1) nstr = 1;
-            if (nstr > cdiv((int)nbricks, 4)) nstr = cdiv((int)nbricks, 4);
-            a.strip = exp_int("OSA_WGRAD_STRIP", (int)cdiv((int)nbricks, (int)nstr));
-            if (a.strip < 1) a.strip = 1;
-            nstr = cdiv((int)nbricks, a.strip);
-            const long long gx = nstr * a.tgroups;
-            const size_t need = (size_t)gx * gy * WG_TAPS * 1024 * sizeof(float);
-            if (query) { *query = need; return 0; }
-            OSA_REQUIRE(ws && ws_bytes >= need && ((size_t)ws & 15) == 0, "conv3d_wgrad_f16x3: workspace of %zu B needed (got %zu)", need, ws_bytes);
-            if (f16x3 == 1) OSA_REQUIRE(x_meta && dy_meta, "conv3d_wgrad_f16x3: range blocks of x and dy required");
-            a.ws = ws;
-            a.Pmeta = dy_meta; a.Qmeta = x_meta;              // (unit-stride conv: P = dy, Q = x)
-            a.Pf16 = dy_f16; a.Qf16 = x_f16;
-            const size_t lds_mt = (size_t)planes * (NA * 32 * 136 + NB * 32 * chs_q) * sizeof(unsigned short);
-            OSA_REQUIRE(lds_mt <= 160 * 1024, "conv3d_wgrad_f16x3: %zu B of LDS", lds_mt);
-            dim3 grid((unsigned)gx, gyb), block(64 * NA * NB);
-#define OSA_WG_MT_LAUNCH(...)                                                                                                         \
-            do { (void)hipFuncSetAttribute((const void*)wgrad_mt_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mt); \
-                 hipLaunchKernelGGL((wgrad_mt_kernel<__VA_ARGS__>), grid, block, lds_mt, st, a); } while (0)
-#define OSA_WG_MT_T(TD_, TH_, TW_, NA_)                                                                                               \
-            if (f16x3 == 1) OSA_WG_MT_LAUNCH(TD_, TH_, TW_, 1, 0, 0, NA_, 2);                                                          \
-            else switch (a.Pf16 * 2 + a.Qf16) {                                                                                       \
-                case 0: OSA_WG_MT_LAUNCH(TD_, TH_, TW_, 0, 0, 0, NA_, 2); break;                                                      \
-                case 1: OSA_WG_MT_LAUNCH(TD_, TH_, TW_, 0, 0, 1, NA_, 2); break;                                                      \
-                case 2: OSA_WG_MT_LAUNCH(TD_, TH_, TW_, 0, 1, 0, NA_, 2); break;                                                      \
-                default: OSA_WG_MT_LAUNCH(TD_, TH_, TW_, 0, 1, 1, NA_, 2); break;                                                     \
-            }
-            if (flat16) { if (NA == 4) { OSA_WG_MT_T(1, 8, 16, 4) } else { OSA_WG_MT_T(1, 8, 16, 2) } }
-            else        { if (NA == 4) { OSA_WG_MT_T(2, 8, 8, 4) } else { OSA_WG_MT_T(2, 8, 8, 2) } }
-#undef OSA_WG_MT_T
-#undef OSA_WG_MT_LAUNCH
-            OSA_LAUNCH_CHECK("conv3d_wgrad_mt");
-            WgradReduceArgs r;
-            memset(&r, 0, sizeof(r));
-            r.ws = ws; r.dW = dw; r.gx = (int)gx; r.tgroups = a.tgroups; r.nstrips = (int)nstr;
-            r.A = a.A; r.Bc = a.Bc; r.kvol = T; r.atiles = atl; r.T = T;
-            r.cls = 1;
-            for (int t2 = 0; t2 < T; ++t2) r.tapid[t2] = (signed char)t2;
-            memcpy(r.g_t0, a.g_t0, sizeof(r.g_t0)); memcpy(r.g_nt, a.g_nt, sizeof(r.g_nt));
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(WG_TAPS * 1024 / 256, a.tgroups, gy), dim3(256), 0, st, r);
-            OSA_LAUNCH_CHECK("conv3d_wgrad_mt_reduce");
-            return 0;
-        }
-        const long long rows = (long long)B * a.tilesD * a.tilesH * a.tgroups * gy;
-        const long long slots = 256ll * 2;                    // (registers: 9 accumulator sets keep both forms at 2 workgroups per CU)
-        long long best = -1; int best_strip = a.tilesW;
-        for (int strip = a.tilesW; strip >= 1; --strip) {
-            const long long wgs = rows * cdiv(a.tilesW, strip);
-            const long long cost = (long long)cdiv(wgs, slots) * (strip + 1);
-            if (best < 0 || cost < best) { best = cost; best_strip = strip; }
-        }
-        a.strip = exp_int("OSA_WGRAD_STRIP", best_strip);
-        if (a.strip < 1 || a.strip > a.tilesW) a.strip = best_strip;
-        const long long gx = (long long)B * a.tilesD * a.tilesH * cdiv(a.tilesW, a.strip) * a.tgroups;
-        OSA_REQUIRE(gx < (1ll << 31) && gy <= 65535, "conv3d_wgrad_f16x3: grid too large");
-        const size_t need = (size_t)gx * gy * WG_TAPS * 1024 * sizeof(float);
-        if (query) { *query = need; return 0; }
-        OSA_REQUIRE(ws && ws_bytes >= need && ((size_t)ws & 15) == 0, "conv3d_wgrad_f16x3: workspace of %zu B needed (got %zu)", need, ws_bytes);
-        if (f16x3 == 1) OSA_REQUIRE(x_meta && dy_meta, "conv3d_wgrad_f16x3: range blocks of x and dy required");
-        a.ws = ws;
-        a.Pmeta = transposed ? x_meta : dy_meta; a.Qmeta = transposed ? dy_meta : x_meta;       // conv: P = dy, Q = x; transposed: P = x, Q = dy
-        a.Pf16 = transposed ? x_f16 : dy_f16; a.Qf16 = transposed ? dy_f16 : x_f16;
-        a.dbg = exp_int("OSA_WG_DBG", 0);
-        dim3 grid((unsigned)gx, gy), block(256);
-        if (f16x3 == 2) {
-#define OSA_WG_F16(TD_, TH_, TW_)                                                                                                    \
-            switch (a.Pf16 * 2 + a.Qf16) {                                                                                           \
-                case 0: hipLaunchKernelGGL((wgrad_f16x3_kernel<TD_, TH_, TW_, 0, 0, 0>), grid, block, lds, st, a); break;              \
-                case 1: hipLaunchKernelGGL((wgrad_f16x3_kernel<TD_, TH_, TW_, 0, 0, 1>), grid, block, lds, st, a); break;              \
-                case 2: hipLaunchKernelGGL((wgrad_f16x3_kernel<TD_, TH_, TW_, 0, 1, 0>), grid, block, lds, st, a); break;              \
-                default: hipLaunchKernelGGL((wgrad_f16x3_kernel<TD_, TH_, TW_, 0, 1, 1>), grid, block, lds, st, a); break;             \
-            }
-            if (flat16) { OSA_WG_F16(1, 8, 16) } else { OSA_WG_F16(2, 8, 8) }
-#undef OSA_WG_F16
-        } else {
-            if (flat16) hipLaunchKernelGGL((wgrad_f16x3_kernel<1, 8, 16, 1>), grid, block, lds, st, a);
-            else hipLaunchKernelGGL((wgrad_f16x3_kernel<2, 8, 8, 1>), grid, block, lds, st, a);
-        }
-        OSA_LAUNCH_CHECK("conv3d_wgrad_f16x3");
-        WgradReduceArgs r;
-        memset(&r, 0, sizeof(r));
-        r.ws = ws; r.dW = dw; r.gx = (int)gx; r.tgroups = a.tgroups; r.nstrips = (int)(gx / a.tgroups);
-        r.A = a.A; r.Bc = a.Bc; r.kvol = T; r.atiles = cdiv(a.A, 32); r.T = T;
-        // the reduce kernel's class mode reads (first tap, count) per group and maps class-major taps back through tapid: used for BOTH modes
-        // here (unit stride: identity tapid), because a group is one z plane of kh * kw taps, not a run of WG_TAPS
-        r.cls = 1;
-        if (a.cls) memcpy(r.tapid, a.tapid, sizeof(r.tapid));
-        else for (int t2 = 0; t2 < T; ++t2) r.tapid[t2] = (signed char)t2;
-        memcpy(r.g_t0, a.g_t0, sizeof(r.g_t0)); memcpy(r.g_nt, a.g_nt, sizeof(r.g_nt));
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(WG_TAPS * 1024 / 256, a.tgroups, gy), dim3(256), 0, st, r);
-        OSA_LAUNCH_CHECK("conv3d_wgrad_f16x3_reduce");
+        a.LH = TH + (o.hmax - a.hmin); a.LW = TW + (o.wmax - a.wmin);
+    }
+    a.LD = TD;
+    a.tgroups = ng;
+    a.tilesD = cdiv(a.Pd, TD); a.tilesH = cdiv(a.Ph, TH); a.tilesW = cdiv(a.Pw, TW);
+    return 0;
+}
+
+// ---- pieces the four launch paths share ------------------------------------------------------------------------------------------------
+// Strip of the kernels that give a workgroup `strip` consecutive w-bricks of one row (fp32 and single-tile f16 family): the one that
+// minimises rounds x (strip + 1), the serial brick count of the busiest CU (+ 1: handing the partial tiles over costs about one brick; a
+// whole row left e.g. 288 workgroups for 256 CUs: two rounds, the second nearly empty).  rows = workgroups at one strip per row, slots =
+// workgroups the GPU holds at once.  `OSA_WGRAD_STRIP` (experiments build) forces one.
+static int pick_strip_rows(long long rows, long long slots, int tilesW) {
+    long long best = -1; int best_strip = tilesW;
+    for (int strip = tilesW; strip >= 1; --strip) {
+        const long long wgs = rows * cdiv(tilesW, strip);
+        const long long cost = (long long)cdiv(wgs, slots) * (strip + 1);
+        if (best < 0 || cost < best) { best = cost; best_strip = strip; }
+    }
+    const int strip = exp_int("OSA_WGRAD_STRIP", best_strip);
+    return (strip < 1 || strip > tilesW) ? best_strip : strip;
+}
+// Strip of the multi-tile kernels, whose workgroups walk a contiguous range of `strip` bricks over (batch, d, h, w): at most `nstr` ranges,
+// at least 4 bricks each (a hand-over is a 36 KB record per wave)
+static int pick_strip_bricks(long long nbricks, long long nstr) {
+    if (nstr > cdiv((int)nbricks, 4)) nstr = cdiv((int)nbricks, 4);
+    if (nstr < 1) nstr = 1;
+    const int strip = exp_int("OSA_WGRAD_STRIP", (int)cdiv((int)nbricks, (int)nstr));
+    return strip < 1 ? 1 : strip;
+}
+// The workspace of the two-stage form, `need` bytes.  1: this was a query and it is answered; 0: go on and launch; -1: error.
+// (form 0 may come without one: float atomics.)
+static int workspace_ok(const WgradProblem& q, size_t need) {
+    if (q.query) { *q.query = need; return 1; }
+    if (!q.form) {
+        if (q.ws) OSA_REQUIRE(q.ws_bytes >= need && ((size_t)q.ws & 15) == 0, "conv3d_wgrad: workspace of %zu B needed (got %zu)", need, q.ws_bytes);
         return 0;
     }
-    const bool two_stage = query || ws;
+    OSA_REQUIRE(q.ws && q.ws_bytes >= need && ((size_t)q.ws & 15) == 0, "conv3d_wgrad_f16x3: workspace of %zu B needed (got %zu)", need, q.ws_bytes);
+    if (q.form == 1) OSA_REQUIRE(q.x_meta && q.dy_meta, "conv3d_wgrad_f16x3: range blocks of x and dy required");
+    return 0;
+}
+static size_t workspace_bytes(long long gx, int gy) { return (size_t)gx * gy * WG_TAPS * 1024 * sizeof(float); }
+// Second stage over the gx x gy records of a launch (gx = strips x tap groups).  The f16 family always uses the reduce kernel's class mode
+// -- (first tap, count) per group, taps mapped back through tapid; unit stride: identity tapid -- because its group is one d offset of
+// kh * kw taps, not a run of WG_TAPS.
+static int launch_reduce(const WgradProblem& q, const WgradArgs& a, long long gx, const char* name) {
+    WgradReduceArgs r;
+    memset(&r, 0, sizeof(r));
+    r.ws = q.ws; r.dW = q.dw; r.gx = (int)gx; r.tgroups = a.tgroups; r.nstrips = (int)(gx / a.tgroups);
+    r.A = a.A; r.Bc = a.Bc; r.kvol = a.T; r.atiles = cdiv(a.A, 32); r.T = a.T;
+    r.cls = q.form ? 1 : a.cls;
+    if (a.cls) memcpy(r.tapid, a.tapid, sizeof(r.tapid));
+    else if (q.form) for (int t = 0; t < a.T; ++t) r.tapid[t] = (signed char)t;
+    memcpy(r.g_t0, a.g_t0, sizeof(r.g_t0)); memcpy(r.g_nt, a.g_nt, sizeof(r.g_nt));
+    const int gy = cdiv(a.A, 32) * cdiv(a.Bc, 32);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(WG_TAPS * 1024 / 256, a.tgroups, gy), dim3(256), 0, (hipStream_t)q.stream, r);
+    OSA_LAUNCH_CHECK(name);
+    return 0;
+}
+// f(SPLIT, PF16, QF16) as compile-time constants: the five variants of every f16-family kernel
+template <int V> using wg_int = std::integral_constant<int, V>;
+template <class F>
+static void wg_f16_dispatch(int form, int pf16, int qf16, F&& f) {
+    if (form == 1) return f(wg_int<1>(), wg_int<0>(), wg_int<0>());
+    switch (pf16 * 2 + qf16) {
+        case 0: return f(wg_int<0>(), wg_int<0>(), wg_int<0>());
+        case 1: return f(wg_int<0>(), wg_int<0>(), wg_int<1>());
+        case 2: return f(wg_int<0>(), wg_int<1>(), wg_int<0>());
+        default: return f(wg_int<0>(), wg_int<1>(), wg_int<1>());
+    }
+}
+template <int TD, int TH, int TW, int NA, int NB, int NG>
+static void launch_mt_kernel(const WgradProblem& q, const WgradArgs& a, dim3 grid, size_t lds) {
+    wg_f16_dispatch(q.form, a.Pf16, a.Qf16, [&](auto split, auto pf16, auto qf16) {
+        const auto kernel = wgrad_mt_kernel<TD, TH, TW, decltype(split)::value, decltype(pf16)::value, decltype(qf16)::value, NA, NB, NG>;
+        (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(kernel, grid, dim3(64 * NA * NB * NG), lds, (hipStream_t)q.stream, a);
+    });
+}
+template <int TD, int TH, int TW>
+static void launch_f16_kernel(const WgradProblem& q, const WgradArgs& a, dim3 grid, size_t lds) {
+    wg_f16_dispatch(q.form, a.Pf16, a.Qf16, [&](auto split, auto pf16, auto qf16) {
+        hipLaunchKernelGGL((wgrad_f16x3_kernel<TD, TH, TW, decltype(split)::value, decltype(pf16)::value, decltype(qf16)::value>), grid, dim3(256), lds, (hipStream_t)q.stream, a);
+    });
+}
+template <int TD, int TH, int TW>
+static void launch_f32_kernel(const WgradProblem& q, const WgradArgs& a, dim3 grid, size_t lds) {
+    (void)hipFuncSetAttribute((const void*)wgrad_kernel<TD, TH, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((wgrad_kernel<TD, TH, TW>), grid, dim3(256), lds, (hipStream_t)q.stream, a);
+}
+static int wg_planes(const WgradProblem& q) { return (q.form == 2) ? 1 : 2; }      // hi (+ lo) planes of P and Q
+
+// ---- the four launch paths -----------------------------------------------------------------------------------------------------------------
+// NG = 3: few channel tiles, 3 x 3 x 3 taps: ONE workgroup per (tile, brick range) with the three kd planes as three groups of waves
+// (two-tile layers spill at 6 waves / 256 registers: they keep the single-tile kernel)
+static int wgrad_launch_g3(const WgradProblem& q, WgradArgs& a) {
+    const long long nbricks = (long long)a.B * a.tilesD * a.tilesH * a.tilesW;
+    OSA_REQUIRE(nbricks < (1ll << 30), "conv3d_wgrad_f16x3: too many position bricks");
+    a.strip = pick_strip_bricks(nbricks, 2 * 256ll);
+    const long long nstr = cdiv((int)nbricks, a.strip), gx = nstr * 3;
+    if (const int r = workspace_ok(q, workspace_bytes(gx, 1))) return r < 0 ? r : 0;
+    a.ws = q.ws;
+    const size_t lds = WgF16Layout<2, 8, 8, 4>::lds_bytes(wg_planes(q), 1, 1);
+    OSA_REQUIRE(lds <= 160 * 1024, "conv3d_wgrad_f16x3: %zu B of LDS", lds);
+    launch_mt_kernel<2, 8, 8, 1, 1, 3>(q, a, dim3((unsigned)nstr, 1), lds);
+    OSA_LAUNCH_CHECK("conv3d_wgrad_mt_g3");
+    return launch_reduce(q, a, gx, "conv3d_wgrad_mt_g3_reduce");
+}
+// multi-tile form: NA x NB tiles per workgroup, ~2 workgroups per CU over the whole launch
+static int wgrad_launch_mt(const WgradProblem& q, WgradArgs& a, bool flat16) {
+    const int atl = cdiv(a.A, 32), btl = cdiv(a.Bc, 32);
+    const int NA = (atl >= 3) ? 4 : 2, NB = 2;
+    const int gyb = cdiv(atl, NA) * cdiv(btl, NB);
+    const long long nbricks = (long long)a.B * a.tilesD * a.tilesH * a.tilesW;
+    OSA_REQUIRE(nbricks < (1ll << 30), "conv3d_wgrad_f16x3: too many position bricks");
+    a.strip = pick_strip_bricks(nbricks, (2 * 256ll) / ((long long)gyb * a.tgroups));
+    const long long nstr = cdiv((int)nbricks, a.strip), gx = nstr * a.tgroups;
+    if (const int r = workspace_ok(q, workspace_bytes(gx, atl * btl))) return r < 0 ? r : 0;
+    a.ws = q.ws;
+    const size_t lds = flat16 ? WgF16Layout<1, 8, 16>::lds_bytes(wg_planes(q), NA, NB) : WgF16Layout<2, 8, 8>::lds_bytes(wg_planes(q), NA, NB);
+    OSA_REQUIRE(lds <= 160 * 1024, "conv3d_wgrad_f16x3: %zu B of LDS", lds);
+    const dim3 grid((unsigned)gx, gyb);
+    if (flat16) { if (NA == 4) launch_mt_kernel<1, 8, 16, 4, 2, 1>(q, a, grid, lds); else launch_mt_kernel<1, 8, 16, 2, 2, 1>(q, a, grid, lds); }
+    else        { if (NA == 4) launch_mt_kernel<2, 8, 8, 4, 2, 1>(q, a, grid, lds); else launch_mt_kernel<2, 8, 8, 2, 2, 1>(q, a, grid, lds); }
+    OSA_LAUNCH_CHECK("conv3d_wgrad_mt");
+    return launch_reduce(q, a, gx, "conv3d_wgrad_mt_reduce");
+}
+// single-tile f16 family: one 32 x 32 tile and one strip of a row of bricks per workgroup; unit stride and class mode
+static int wgrad_launch_f16(const WgradProblem& q, WgradArgs& a, bool flat16) {
+    const int gy = cdiv(a.A, 32) * cdiv(a.Bc, 32);
+    // slots: two workgroups per CU.  (The kernel compiles to 178 VGPRs + 144 AGPRs, i.e. ONE wave per SIMD and one workgroup per CU: the
+    // figure is kept because it is what the strip was tuned with -- see profiles/round9/wgrad_one_definition.md.)
+    a.strip = pick_strip_rows((long long)a.B * a.tilesD * a.tilesH * a.tgroups * gy, 256ll * 2, a.tilesW);
+    const long long gx = (long long)a.B * a.tilesD * a.tilesH * cdiv(a.tilesW, a.strip) * a.tgroups;
+    OSA_REQUIRE(gx < (1ll << 31) && gy <= 65535, "conv3d_wgrad_f16x3: grid too large");
+    if (const int r = workspace_ok(q, workspace_bytes(gx, gy))) return r < 0 ? r : 0;
+    a.ws = q.ws;
+    a.dbg = exp_int("OSA_WG_DBG", 0);
+    const size_t lds_ops = flat16 ? WgF16Layout<1, 8, 16>::lds_bytes(wg_planes(q), 1, 1) : WgF16Layout<2, 8, 8>::lds_bytes(wg_planes(q), 1, 1);
+    const size_t lds_red = (size_t)3 * 16 * 64 * sizeof(float);          // the hand-over of the partial tiles reuses the LDS: 3 waves x 16 x 64 floats
+    const size_t lds = lds_ops > lds_red ? lds_ops : lds_red;
+    const dim3 grid((unsigned)gx, gy);
+    if (flat16) launch_f16_kernel<1, 8, 16>(q, a, grid, lds); else launch_f16_kernel<2, 8, 8>(q, a, grid, lds);
+    OSA_LAUNCH_CHECK("conv3d_wgrad_f16x3");
+    return launch_reduce(q, a, gx, "conv3d_wgrad_f16x3_reduce");
+}
+// exact fp32 kernel, two-stage or (no workspace) float atomics
+static int wgrad_launch_f32(const WgradProblem& q, WgradArgs& a, const WgOffsets& o) {
+    const bool two_stage = q.query || q.ws;
     if (!two_stage) {
-        hipError_t e = hipMemsetAsync(dw, 0, (size_t)a.A * a.Bc * T * sizeof(float), st);
+        hipError_t e = hipMemsetAsync(q.dw, 0, (size_t)a.A * a.Bc * a.T * sizeof(float), (hipStream_t)q.stream);
         OSA_REQUIRE(e == hipSuccess, "conv3d_wgrad: memset failed: %s", hipGetErrorString(e));
     }
     // Position brick: 4x8x8 (256 positions, 1 workgroup per CU with its ~95-122 KB of LDS) or 2x8x8 (128 positions, 2 per CU: the
     // staging of one overlaps the MFMAs of the other).  `OSA_WGRAD_TD` (experiments build) forces one.
     // Flat (D = 1) layers -- the 2-D convs of the update block and of the upsampling heads -- take a 1x16x16 brick: a 4x8x8 one would
     // spend three of its four planes on padding.
-    const bool flat = (a.Pd == 1 && kd == 1);
+    const bool flat = (a.Pd == 1 && q.d.kd == 1);
     const int TW = flat ? 16 : 8, TH = flat ? 16 : 8;
     int TD = flat ? 1 : exp_int("OSA_WGRAD_TD", 4);
     if (!flat && TD != 2 && TD != 4) TD = 4;
-    a.LD = (TD - 1) * a.s + (dmax - a.dmin) + 1;
-    a.LH = (TH - 1) * a.s + (hmax - a.hmin) + 1;
-    a.LW = (TW - 1) * a.s + (wmax - a.wmin) + 1;
+    a.LD = (TD - 1) * a.s + (o.dmax - a.dmin) + 1;
+    a.LH = (TH - 1) * a.s + (o.hmax - a.hmin) + 1;
+    a.LW = (TW - 1) * a.s + (o.wmax - a.wmin) + 1;
     if (a.cls) { a.LD = TD + 1; a.LH = TH + 1; a.LW = TW + 1; }          // class sub-lattice: delta in {dmin, dmin + 1}
     a.tilesD = cdiv(a.Pd, TD); a.tilesH = cdiv(a.Ph, TH); a.tilesW = cdiv(a.Pw, TW);
     const size_t lds = ((size_t)TD * TH * TW + (size_t)a.LD * a.LH * a.LW) * WG_PS * sizeof(float);
     OSA_REQUIRE(lds <= 160 * 1024, "conv3d_wgrad: %zu B of LDS needed", lds);
     const int gy = cdiv(a.A, 32) * cdiv(a.Bc, 32);
-    // Strip = consecutive w-bricks one workgroup accumulates before it hands its partial tiles over.  Atomics form: a whole row per
-    // workgroup (every extra workgroup costs a round of ~9 K contended float atomics).  Two-stage form: the hand-over is 36 KB of plain
-    // stores, so the strip is chosen for load balance -- the one that minimises rounds x (strip + 1), the serial brick count of the
-    // busiest CU (a whole row left e.g. 288 workgroups for 256 CUs: two rounds, the second nearly empty).
-    a.strip = a.tilesW;
-    if (two_stage) {
-        const long long rows = (long long)B * a.tilesD * a.tilesH * a.tgroups * gy;
-        const long long slots = 256ll * ((lds <= 80 * 1024) ? 2 : 1);
-        long long best = -1; int best_strip = a.tilesW;
-        for (int strip = a.tilesW; strip >= 1; --strip) {
-            const long long wgs = rows * cdiv(a.tilesW, strip);
-            const long long cost = (long long)cdiv(wgs, slots) * (strip + 1);    // + 1: the atomics round of a workgroup costs about one brick
-            if (best < 0 || cost < best) { best = cost; best_strip = strip; }
-        }
-        a.strip = exp_int("OSA_WGRAD_STRIP", best_strip);
-        if (a.strip < 1 || a.strip > a.tilesW) a.strip = best_strip;
-    }
-    const long long gx = (long long)B * a.tilesD * a.tilesH * cdiv(a.tilesW, a.strip) * a.tgroups;
+    // Atomics form: a whole row per workgroup (every extra workgroup costs a round of ~9 K contended float atomics).  Two-stage form: the
+    // hand-over is 36 KB of plain stores, so the strip is chosen for load balance.
+    a.strip = two_stage ? pick_strip_rows((long long)a.B * a.tilesD * a.tilesH * a.tgroups * gy, 256ll * ((lds <= 80 * 1024) ? 2 : 1), a.tilesW) : a.tilesW;
+    const long long gx = (long long)a.B * a.tilesD * a.tilesH * cdiv(a.tilesW, a.strip) * a.tgroups;
     OSA_REQUIRE(gx < (1ll << 31) && gy <= 65535, "conv3d_wgrad: grid too large");
-    const size_t need = (size_t)gx * gy * WG_TAPS * 1024 * sizeof(float);
-    if (query) { *query = need; return 0; }
-    if (ws) OSA_REQUIRE(ws_bytes >= need && ((size_t)ws & 15) == 0, "conv3d_wgrad: workspace of %zu B needed (got %zu)", need, ws_bytes);
-    a.ws = ws;
-    dim3 grid((unsigned)gx, gy), block(256);
-    if (flat) {
-        (void)hipFuncSetAttribute((const void*)wgrad_kernel<1, 16, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((wgrad_kernel<1, 16, 16>), grid, block, lds, st, a);
-    } else if (TD == 2) {
-        (void)hipFuncSetAttribute((const void*)wgrad_kernel<2, 8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((wgrad_kernel<2, 8, 8>), grid, block, lds, st, a);
-    } else {
-        (void)hipFuncSetAttribute((const void*)wgrad_kernel<4, 8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((wgrad_kernel<4, 8, 8>), grid, block, lds, st, a);
-    }
+    if (const int r = workspace_ok(q, workspace_bytes(gx, gy))) return r < 0 ? r : 0;
+    a.ws = q.ws;
+    const dim3 grid((unsigned)gx, gy);
+    if (flat) launch_f32_kernel<1, 16, 16>(q, a, grid, lds);
+    else if (TD == 2) launch_f32_kernel<2, 8, 8>(q, a, grid, lds);
+    else launch_f32_kernel<4, 8, 8>(q, a, grid, lds);
     OSA_LAUNCH_CHECK("conv3d_wgrad");
-    if (ws) {
-        WgradReduceArgs r;
-        memset(&r, 0, sizeof(r));
-        r.ws = ws; r.dW = dw; r.gx = (int)gx; r.tgroups = a.tgroups; r.nstrips = (int)(gx / a.tgroups);
-        r.A = a.A; r.Bc = a.Bc; r.kvol = T; r.atiles = cdiv(a.A, 32); r.T = T; r.cls = a.cls;
-        memcpy(r.tapid, a.tapid, sizeof(r.tapid)); memcpy(r.g_t0, a.g_t0, sizeof(r.g_t0)); memcpy(r.g_nt, a.g_nt, sizeof(r.g_nt));
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(WG_TAPS * 1024 / 256, a.tgroups, gy), dim3(256), 0, st, r);
-        OSA_LAUNCH_CHECK("conv3d_wgrad_reduce");
-    }
-    return 0;
+    return q.ws ? launch_reduce(q, a, gx, "conv3d_wgrad_reduce") : 0;
+}
+
+static int wgrad_impl(const WgradProblem& q) {
+    WgradArgs a;
+    WgOffsets o;
+    if (const int e = wgrad_setup(q, a, o)) return e;
+    if (!q.form) return wgrad_launch_f32(q, a, o);
+    // f16 family: unit dilation; unit stride with <= 3x3 planes, or the stride-2 / transposed layers in class mode.  Not eligible ->
+    // *query = 0 / error: the caller keeps the fp32 form.
+    const WgradDims& d = q.d;
+    bool ok = d.dil_d == 1 && d.dil_h == 1 && d.dil_w == 1;
+    if (a.s == 1) ok = ok && !d.transposed && d.kh <= 3 && d.kw <= 3;
+    if (q.query && !ok) { *q.query = 0; return 0; }
+    OSA_REQUIRE(ok, "conv3d_wgrad_f16x3: layer not eligible (unit dilation; unit-stride layers: kh, kw <= 3)");
+    const bool flat16 = (a.Pd == 1 && d.kd == 1);
+    if (const int e = wgrad_f16_groups(a, o, d.kd, flat16)) return e;
+    const int tiles = cdiv(a.A, 32) * cdiv(a.Bc, 32);
+    const bool multi_tile = !a.cls && g_wgrad_mt;          // (class mode keeps the single-tile kernel)
+    if (multi_tile && !flat16 && d.kd == 3 && a.tgroups == 3 && tiles == 1 && a.g_od[0] == a.dmin && a.g_od[1] == a.dmin + 1 && a.g_od[2] == a.dmin + 2)
+        return wgrad_launch_g3(q, a);
+    if (multi_tile && tiles >= 4) return wgrad_launch_mt(q, a, flat16);
+    return wgrad_launch_f16(q, a, flat16);
 }
 
 extern "C" int osa_conv3d_wgrad_f32(const float* x, const float* dy, float* dw,
@@ -1139,17 +1070,23 @@ extern "C" int osa_conv3d_wgrad_f32(const float* x, const float* dy, float* dw,
                                     int kd, int kh, int kw, int stride,
                                     int pad_d, int pad_h, int pad_w, int dil_d, int dil_h, int dil_w,
                                     int transposed, void* stream) {
-    return wgrad_impl(x, dy, dw, B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w,
-                      dil_d, dil_h, dil_w, transposed, nullptr, 0, nullptr, stream);
+    WgradProblem q{{B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed}};
+    q.x = x; q.dy = dy; q.dw = dw; q.stream = stream;
+    return wgrad_impl(q);
+}
+
+// both workspace queries; 0 when the form does not cover the layer (or the dimensions are refused)
+static size_t wgrad_query(const WgradDims& d, int form) {
+    size_t need = 0;
+    WgradProblem q{d, form};
+    q.query = &need;
+    return wgrad_impl(q) ? 0 : need;
 }
 
 extern "C" size_t osa_conv3d_wgrad_workspace_bytes(int B, int Di, int Hi, int Wi, int Ci, int Do, int Ho, int Wo, int Co,
                                                    int kd, int kh, int kw, int stride, int pad_d, int pad_h, int pad_w,
                                                    int dil_d, int dil_h, int dil_w, int transposed) {
-    size_t need = 0;
-    if (wgrad_impl(nullptr, nullptr, nullptr, B, Di, Hi, Wi, Ci, 4, Do, Ho, Wo, Co, 4, kd, kh, kw, stride, pad_d, pad_h, pad_w,
-                   dil_d, dil_h, dil_w, transposed, nullptr, 0, &need, nullptr)) return 0;
-    return need;
+    return wgrad_query({B, Di, Hi, Wi, Ci, 4, Do, Ho, Wo, Co, 4, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed}, 0);
 }
 
 extern "C" int osa_conv3d_wgrad_ws_f32(const float* x, const float* dy, float* dw,
@@ -1159,19 +1096,17 @@ extern "C" int osa_conv3d_wgrad_ws_f32(const float* x, const float* dy, float* d
                                        int pad_d, int pad_h, int pad_w, int dil_d, int dil_h, int dil_w,
                                        int transposed, float* workspace, size_t workspace_bytes, void* stream) {
     OSA_REQUIRE(workspace, "conv3d_wgrad_ws: NULL workspace (osa_conv3d_wgrad_workspace_bytes gives its size)");
-    return wgrad_impl(x, dy, dw, B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w,
-                      dil_d, dil_h, dil_w, transposed, workspace, workspace_bytes, nullptr, stream);
+    WgradProblem q{{B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed}};
+    q.x = x; q.dy = dy; q.dw = dw; q.ws = workspace; q.ws_bytes = workspace_bytes; q.stream = stream;
+    return wgrad_impl(q);
 }
 
 /* split-precision (f16x3) weight gradient, two-stage form only.  workspace_bytes query returns 0 for layers the form does not cover
- * (strided / dilated / transposed layers, kernels wider than 3): the caller then uses osa_conv3d_wgrad_ws_f32. */
+ * (dilated layers, unit-stride kernels wider than 3): the caller then uses osa_conv3d_wgrad_ws_f32. */
 extern "C" size_t osa_conv3d_wgrad_f16x3_workspace_bytes(int B, int Di, int Hi, int Wi, int Ci, int Do, int Ho, int Wo, int Co,
                                                          int kd, int kh, int kw, int stride, int pad_d, int pad_h, int pad_w,
                                                          int dil_d, int dil_h, int dil_w, int transposed) {
-    size_t need = 0;
-    if (wgrad_impl(nullptr, nullptr, nullptr, B, Di, Hi, Wi, Ci, 4, Do, Ho, Wo, Co, 4, kd, kh, kw, stride, pad_d, pad_h, pad_w,
-                   dil_d, dil_h, dil_w, transposed, nullptr, 0, &need, nullptr, 1)) return 0;
-    return need;
+    return wgrad_query({B, Di, Hi, Wi, Ci, 4, Do, Ho, Wo, Co, 4, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed}, 1);
 }
 
 extern "C" int osa_conv3d_wgrad_ws_f16x3(const float* x, const float* dy, float* dw,
@@ -1182,8 +1117,10 @@ extern "C" int osa_conv3d_wgrad_ws_f16x3(const float* x, const float* dy, float*
                                          int transposed, const float* x_meta, const float* dy_meta,
                                          float* workspace, size_t workspace_bytes, void* stream) {
     OSA_REQUIRE(workspace, "conv3d_wgrad_ws_f16x3: NULL workspace (osa_conv3d_wgrad_f16x3_workspace_bytes gives its size)");
-    return wgrad_impl(x, dy, dw, B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w,
-                      dil_d, dil_h, dil_w, transposed, workspace, workspace_bytes, nullptr, stream, 1, x_meta, dy_meta);
+    WgradProblem q{{B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed}, 1};
+    q.x = x; q.dy = dy; q.dw = dw; q.x_meta = x_meta; q.dy_meta = dy_meta;
+    q.ws = workspace; q.ws_bytes = workspace_bytes; q.stream = stream;
+    return wgrad_impl(q);
 }
 
 /* native f16 weight gradient (r5): the arithmetic of the reference's AMP training -- fp16 operands (rounded to nearest even when staged),
@@ -1197,9 +1134,10 @@ extern "C" int osa_conv3d_wgrad_ws_f16(const void* x, const void* dy, float* dw,
                                        int transposed, const float* x_meta, const float* dy_meta, int x_f16, int dy_f16,
                                        float* workspace, size_t workspace_bytes, void* stream) {
     OSA_REQUIRE(workspace, "conv3d_wgrad_ws_f16: NULL workspace (osa_conv3d_wgrad_f16x3_workspace_bytes gives its size)");
-    return wgrad_impl(static_cast<const float*>(x), static_cast<const float*>(dy), dw, B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride,
-                      pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed, workspace, workspace_bytes, nullptr, stream, 2, x_meta, dy_meta,
-                      x_f16 ? 1 : 0, dy_f16 ? 1 : 0);
+    WgradProblem q{{B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed}, 2};
+    q.x = x; q.dy = dy; q.dw = dw; q.x_meta = x_meta; q.dy_meta = dy_meta; q.x_f16 = x_f16 ? 1 : 0; q.dy_f16 = dy_f16 ? 1 : 0;
+    q.ws = workspace; q.ws_bytes = workspace_bytes; q.stream = stream;
+    return wgrad_impl(q);
 }
 
 /* The weight gradient over a LIST of equally shaped (x, dy) tensor pairs -- the uses of one weight within a training step (the update
@@ -1215,7 +1153,9 @@ extern "C" int osa_conv3d_wgrad_ws_multi(int form, const void* const* xs, const 
                                          float* workspace, size_t workspace_bytes, void* stream) {
     OSA_REQUIRE(workspace && xs && dys && n_items >= 1 && n_items <= 24, "conv3d_wgrad_ws_multi: NULL workspace / lists, or n_items %d outside 1..24", n_items);
     OSA_REQUIRE(form >= 0 && form <= 2 && (form == 2 || (!x_f16 && !dy_f16)), "conv3d_wgrad_ws_multi: form %d (fp16 tensors exist in form 2 only)", form);
-    return wgrad_impl(static_cast<const float*>(xs[0]), static_cast<const float*>(dys[0]), dw, B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride,
-                      pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed, workspace, workspace_bytes, nullptr, stream, form, x_meta, dy_meta,
-                      x_f16 ? 1 : 0, dy_f16 ? 1 : 0, xs, dys, n_items);
+    WgradProblem q{{B, Di, Hi, Wi, Ci, xCs, Do, Ho, Wo, Co, dyCs, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w, transposed}, form};
+    q.x = xs[0]; q.dy = dys[0]; q.dw = dw; q.x_meta = x_meta; q.dy_meta = dy_meta; q.x_f16 = x_f16 ? 1 : 0; q.dy_f16 = dy_f16 ? 1 : 0;
+    q.x_tab = xs; q.dy_tab = dys; q.n_tab = n_items;
+    q.ws = workspace; q.ws_bytes = workspace_bytes; q.stream = stream;
+    return wgrad_impl(q);
 }

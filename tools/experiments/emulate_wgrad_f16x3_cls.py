@@ -1,6 +1,6 @@
 """CPU emulation of wgrad_f16x3_kernel's CLASS MODE index arithmetic (stride-2 convs and stride-2 transposed convs): parity classes, tap
 groups by d delta, sub-lattice staging (tensor coordinate = 2 * (p0 + delta_min + l) + par), slot table, fragment windows -- against
-torch autograd of F.conv3d / F.conv_transpose3d.  Mirrors the host tables of wgrad_impl and the kernel's addressing (csrc/wgrad.hip)."""
+torch autograd of F.conv3d / F.conv_transpose3d.  Mirrors the host tables of wgrad_setup / wgrad_f16_groups and the kernel's addressing (csrc/wgrad.hip)."""
 import itertools
 import numpy as np
 import torch
