@@ -34,6 +34,8 @@
  *                               models/psmnet/psmnet_cost_processor.py:201-214
  *   osa_*softargmin_var_f32     the three heads with disparity_variance beside the disparity,
  *                               models/cfnet/submodule.py:128-134, models/igevpp/submodule.py:153-159
+ *   osa_geo_lookup_mr_*_f32     the multi-range lookup of IGEV++'s GRU loop (three geometry volumes of different disparity
+ *                               ranges + the correlation pyramid -> four tensors), models/igevpp/geometry.py:6-87
  */
 #ifndef OPENSTEREO_AMD_H
 #define OPENSTEREO_AMD_H
@@ -44,7 +46,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 9
+#define OSA_ABI_VERSION 10
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -601,6 +603,41 @@ int osa_geo_lookup_bwd_acc_f32(float* const* dgeo_levels, float* const* dcorr_le
                                const int* geo_len, const int* corr_len, int levels,
                                const float* disp, const float* coords_x, const float* dout,
                                int B, int H, int W, int C, int radius, void* stream);
+
+/* ---- multi-range lookup of IGEV++ (models/igevpp/geometry.py:6-87) ---------- */
+/* One GRU-iteration lookup of Combined_Geo_Encoding_Volume.__call__ in ONE launch.  Sources (T = 2r+1 taps dx = -r..r each, 1-D linear,
+ * zero padding, the float32 position round trip of bilinear_sampler):
+ *   geo0_levels[l] rows [B,H,W,C,geo0_len[l]]  at dx + disp/2^l                    -> geo_feat0 [B, levels*C*T, H, W], channel l*C*T + c*T + k
+ *   geo1           rows [B,H,W,C,geo1_len]     at dx + disp/2                      -> geo_feat1 [B, C*T, H, W],        channel c*T + k
+ *   geo2           rows [B,H,W,C,geo2_len]     at dx + disp/4                      -> geo_feat2 [B, C*T, H, W],        channel c*T + k
+ *   corr_levels[l] rows [B,H,W,corr_len[l]]    at coords/2^l - disp/2^l + dx       -> init_corr [B, levels*T, H, W],   channel l*T + k
+ * geo0_levels / corr_levels / geo0_len / corr_len: HOST arrays (levels = 1..4); disp, coords_x [B,H,W]. */
+int osa_geo_lookup_mr_f32(const float* const* geo0_levels, const float* const* corr_levels,
+                          const int* geo0_len, const int* corr_len, int levels,
+                          const float* geo1, int geo1_len, const float* geo2, int geo2_len,
+                          const float* disp, const float* coords_x,
+                          float* geo_feat0, float* geo_feat1, float* geo_feat2, float* init_corr,
+                          int B, int H, int W, int C, int radius, void* stream);
+/* The same lookup, channels-last: four tensors [B,H,W,cs] with their own channel strides (cs0 / cs1 / cs2 for geo_feat0 / 1 / 2, cs_corr
+ * for init_corr), channel index as above, channels beyond a tensor's count zero-filled -- what the 1x1 convg1 / convc1 layers of IGEV++'s
+ * GeoEncoder read (igevpp/update.py:72-80). */
+int osa_geo_lookup_mr_nhwc_f32(const float* const* geo0_levels, const float* const* corr_levels,
+                               const int* geo0_len, const int* corr_len, int levels,
+                               const float* geo1, int geo1_len, const float* geo2, int geo2_len,
+                               const float* disp, const float* coords_x,
+                               float* geo_feat0, float* geo_feat1, float* geo_feat2, float* init_corr,
+                               int cs0, int cs1, int cs2, int cs_corr,
+                               int B, int H, int W, int C, int radius, void* stream);
+/* Gradient of osa_geo_lookup_mr_f32 with respect to all 2 * levels + 2 sources, ACCUMULATED into buffers of the sources' shapes that the
+ * caller zero-fills once per training step (as osa_geo_lookup_bwd_acc_f32: a window of 2r+3 positions per row, one lane per position, no
+ * atomics, taps added in ascending order).  The disparity is detached in the reference's loop (igevpp_stereo.py:221) and gets none.
+ * dfeat0 / dfeat1 / dfeat2 / dcorr_out: upstream gradients of the four NCHW outputs.  radius <= 30, row lengths <= 2^19. */
+int osa_geo_lookup_mr_bwd_acc_f32(float* const* dgeo0_levels, float* const* dcorr_levels,
+                                  const int* geo0_len, const int* corr_len, int levels,
+                                  float* dgeo1, int geo1_len, float* dgeo2, int geo2_len,
+                                  const float* disp, const float* coords_x,
+                                  const float* dfeat0, const float* dfeat1, const float* dfeat2, const float* dcorr_out,
+                                  int B, int H, int W, int C, int radius, void* stream);
 
 /* ---- input pre-processing on device ------------------------- */
 /* RightTopPad(edge) + HWC->CHW + /255 + (x-mean)/std for the left and right image in one launch

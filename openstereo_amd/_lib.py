@@ -41,6 +41,7 @@ c_ref = C.POINTER(NhwcRef)
 
 # name -> (restype, argtypes).  Mirrors include/openstereo_amd.h one to one; tests check that
 # every symbol declared in the header is listed here and exported by the .so.
+_LEVELS = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i), C.POINTER(c_i), c_i]   # geo / corr pointer and length arrays (host), levels
 SIGNATURES = {
     "osa_abi_version": (c_i, []),
     "osa_last_error": (C.c_char_p, []),
@@ -160,14 +161,13 @@ SIGNATURES = {
     "osa_allpairs_corr_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_geo_rows_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_avgpool_rows_f32": (c_i, [c_fp, c_fp, c_ll, c_i, c_st]),
-    "osa_geo_lookup_f32": (c_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i), C.POINTER(c_i), c_i,
-                                 c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_geo_lookup_nhwc_f32": (c_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i), C.POINTER(c_i), c_i,
-                                      c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_geo_lookup_bwd_acc_f32": (c_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i), C.POINTER(c_i), c_i,
-                                         c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_geo_lookup_bwd_f32": (c_i, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i), C.POINTER(c_i), c_i,
-                                     c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_geo_lookup_f32": (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_geo_lookup_nhwc_f32": (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_geo_lookup_bwd_acc_f32": (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_geo_lookup_bwd_f32": (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_geo_lookup_mr_f32": (c_i, _LEVELS + [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_geo_lookup_mr_nhwc_f32": (c_i, _LEVELS + [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_geo_lookup_mr_bwd_acc_f32": (c_i, _LEVELS + [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_preprocess_pair_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), C.POINTER(c_f), c_fp, c_i, c_st]),
     "osa_conv3d_pack_f16": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_deconv3d_pack_f16": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),

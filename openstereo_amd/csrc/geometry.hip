@@ -12,6 +12,7 @@
 // All memory-bound; lanes run along w (outputs) or along the contiguous row axis (transposes).
 #include "osa_common.h"
 #include <cstring>
+#include <type_traits>
 
 namespace osa {
 
@@ -165,28 +166,9 @@ __global__ __launch_bounds__(256) void geo_lookup_rows_kernel(const LookupArgs p
     }
 }
 
-// Channels-last form for the engine's GRU loop: out [B,H,W,Cs] (Cs >= channels, the padding zero-filled), i.e. what the update
-// block's 1x1 convc1 reads -- the NCHW result of the kernel above had to be transposed every iteration (85 MB at 4 pairs).  One thread =
-// one (pixel, row): row j < levels * (C + 1) is geometry row c of level l or that level's correlation row, and produces the 2r + 1 taps of
-// its row = 2r + 1 consecutive output channels, so the threads of a pixel write its channel vector contiguously; 18x the threads of the
-// per-pixel kernel and 18 loads per thread instead of 324.  Same tap arithmetic (tap_of / sample_row), same values.
+// The 2r + 1 taps of one row into 2r + 1 consecutive floats (the channels-last kernels): `x` is the row's position without the tap offset.
 template <int TAPS>      // TAPS = 2 * radius + 1 known at compile time (9 in every shipped config), 0 = generic
-__global__ __launch_bounds__(256) void geo_lookup_nhwc_kernel(const LookupArgs p, int Cs) {
-    const int rows_per_px = p.levels * (p.C + 1);
-    const unsigned npix = (unsigned)p.B * p.H * p.W;                // host: B*H*W*rows < 2^31
-    const unsigned t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= npix * (unsigned)rows_per_px) return;
-    const unsigned i = t / (unsigned)rows_per_px;
-    const int j = (int)(t - i * (unsigned)rows_per_px);
-    const int l = j / (p.C + 1), c = j - l * (p.C + 1);
-    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
-    const float scale = 1.f / (float)(1 << l);                     // exact: the per-pixel kernel multiplies 0.5f l times
-    const float d = p.disp[i], cx = p.coords[i];
-    float* o = p.out + (size_t)i * Cs + (size_t)j * taps;
-    const bool is_corr = (c == p.C);
-    const int n = is_corr ? p.Wl[l] : p.Dl[l];
-    const float* row = is_corr ? p.corr[l] + (size_t)i * p.Wl[l] : p.geo[l] + ((size_t)i * p.C + c) * p.Dl[l];
-    const float x = is_corr ? (cx * scale - d * scale) : d * scale;
+__device__ __forceinline__ void row_taps_cl(const float* __restrict__ row, int n, float x, bool is_corr, int radius, float* __restrict__ o) {
     if constexpr (TAPS > 0) {
         // all loads first, unconditionally (index clamped into the row, the value dropped by a select): 2 * TAPS independent requests
         // in flight per thread instead of a branch and a wait per tap
@@ -206,11 +188,36 @@ __global__ __launch_bounds__(256) void geo_lookup_nhwc_kernel(const LookupArgs p
             o[k] = av * tp[k].w0 + bv * tp[k].w1;                   // == sample_row
         }
     } else {
-        for (int k = 0; k < taps; ++k) {
-            const float dx = (float)(k - p.radius);
+        for (int k = 0; k < 2 * radius + 1; ++k) {
+            const float dx = (float)(k - radius);
             o[k] = sample_row(row, n, tap_of(is_corr ? x + dx : dx + x, n));
         }
     }
+}
+
+// Channels-last form for the engine's GRU loop: out [B,H,W,Cs] (Cs >= channels, the padding zero-filled), i.e. what the update
+// block's 1x1 convc1 reads -- the NCHW result of the kernel above had to be transposed every iteration (85 MB at 4 pairs).  One thread =
+// one (pixel, row): row j < levels * (C + 1) is geometry row c of level l or that level's correlation row, and produces the 2r + 1 taps of
+// its row = 2r + 1 consecutive output channels, so the threads of a pixel write its channel vector contiguously; 18x the threads of the
+// per-pixel kernel and 18 loads per thread instead of 324.  Same tap arithmetic (tap_of / sample_row), same values.
+template <int TAPS>
+__global__ __launch_bounds__(256) void geo_lookup_nhwc_kernel(const LookupArgs p, int Cs) {
+    const int rows_per_px = p.levels * (p.C + 1);
+    const unsigned npix = (unsigned)p.B * p.H * p.W;                // host: B*H*W*rows < 2^31
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= npix * (unsigned)rows_per_px) return;
+    const unsigned i = t / (unsigned)rows_per_px;
+    const int j = (int)(t - i * (unsigned)rows_per_px);
+    const int l = j / (p.C + 1), c = j - l * (p.C + 1);
+    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
+    const float scale = 1.f / (float)(1 << l);                     // exact: the per-pixel kernel multiplies 0.5f l times
+    const float d = p.disp[i], cx = p.coords[i];
+    float* o = p.out + (size_t)i * Cs + (size_t)j * taps;
+    const bool is_corr = (c == p.C);
+    const int n = is_corr ? p.Wl[l] : p.Dl[l];
+    const float* row = is_corr ? p.corr[l] + (size_t)i * p.Wl[l] : p.geo[l] + ((size_t)i * p.C + c) * p.Dl[l];
+    const float x = is_corr ? (cx * scale - d * scale) : d * scale;
+    row_taps_cl<TAPS>(row, n, x, is_corr, p.radius, o);
     if (j == rows_per_px - 1)
         for (int k = rows_per_px * taps; k < Cs; ++k) p.out[(size_t)i * Cs + k] = 0.f;
 }
@@ -393,6 +400,33 @@ __global__ __launch_bounds__(256) void geo_lookup_bwd_rows_kernel(const LookupBw
 // positions x0(tap 0) .. x0(tap 0) + 2r + 2, and position x0(tap 0) + e can only be reached by taps e - 2 .. e + 1.
 // Lanes: a row takes G = 2r + 3 consecutive lanes of a wave, 64 / G rows per wave (5 of the 9-tap rows: 55 lanes).  Lane e < 2r + 1 evaluates
 // tap e and loads its upstream gradient -- once per tap -- and the lanes of a row exchange (x0, g * w0, g * w1) by shuffles.
+
+// The window of one row, shared by the accumulating kernels: lane e of the row's G = taps + 2 lanes (e < taps: tap e, whose upstream gradient is
+// o[e * ostride]) adds what the taps e - 2 .. e + 1 put on position j = x0(tap 0) + e of its row, at entry(j) (asked for by the lanes that store only).
+// Every lane of the wave calls it (shuffles).
+template <class Entry>
+__device__ __forceinline__ void acc_row_window(int taps, int lane, int e, bool row_on, float x, int n, const float* __restrict__ o, size_t ostride,
+                                               Entry entry) {
+    const Tap tk = tap_of((float)(e - taps / 2) + x, n);                 // (lanes e >= taps: evaluated, never used)
+    const float ov = (row_on && e < taps) ? o[(size_t)e * ostride] : 0.f;
+    const int x0 = tk.x0;
+    const float t0 = ov * tk.w0, t1 = ov * tk.w1;
+    const int j = __shfl(x0, lane - e) + e;                              // this lane's position
+    float v = 0.f;
+    bool hit = false;
+#pragma unroll
+    for (int q = -2; q <= 1; ++q) {                                      // taps e - 2 .. e + 1 of this row, ascending
+        const int src = (lane + q) & 63;
+        const int xs = __shfl(x0, src);
+        const float a0 = __shfl(t0, src), a1 = __shfl(t1, src);
+        const bool on = e + q >= 0 && e + q < taps;                      // (then lane + q is a lane of this row)
+        if (on && xs == j) { v += a0; hit = true; }
+        if (on && xs + 1 == j) { v += a1; hit = true; }
+    }
+    if (!row_on || !hit || j < 0 || j >= n) return;
+    *entry(j) += v;
+}
+
 template <int TAPS>      // TAPS = 2 * radius + 1 known at compile time (9 in every shipped config), 0 = generic
 __global__ __launch_bounds__(256) void geo_lookup_bwd_acc_kernel(const LookupBwdGatherArgs p) {
     const unsigned HW = (unsigned)p.H * p.W;
@@ -417,25 +451,104 @@ __global__ __launch_bounds__(256) void geo_lookup_bwd_acc_kernel(const LookupBwd
     const int n = geo ? p.Dl[l] : p.Wl[l];
     const int per_level = (p.C + 1) * taps;
     const float* o = p.dout + (size_t)b * per_level * p.levels * HW + hw + ((size_t)l * per_level + (size_t)c * taps) * HW;
-    const Tap tk = tap_of((float)(e - taps / 2) + x, n);                 // (lanes e >= taps: evaluated, never used)
-    const float ov = (row_on && e < taps) ? o[(size_t)e * HW] : 0.f;
-    const int x0 = tk.x0;
-    const float t0 = ov * tk.w0, t1 = ov * tk.w1;
-    const int j = __shfl(x0, lane - e) + e;                              // this lane's position
-    float v = 0.f;
-    bool hit = false;
+    acc_row_window(taps, lane, e, row_on, x, n, o, HW, [&](int pos) { return geo ? p.dgeo[l] + ((size_t)i * p.C + c) * n + pos : p.dcorr[l] + (size_t)i * n + pos; });
+}
+
+
+// ---- multi-range lookup of IGEV++ (models/igevpp/geometry.py:6-87): volume 0 with an averaged pyramid at disp / 2^l, volumes 1 and 2 (no
+// pyramid) at disp / 2 and disp / 4, the correlation pyramid at coords / 2^l - disp / 2^l; four output tensors (geo_feat0 / 1 / 2, init_corr).
+// A lookup is a short list of SOURCES passed by value: per source the rows, their length, rows per pixel, an exact power-of-two scale, the
+// kind of position and where its taps go.  The three kernels below are the rows / channels-last / accumulating kernels above over that list:
+// same tap_of / sample_row, same operand order, so a source gives bit for bit what the single-pyramid kernels give for the same rows.
+struct LookupSrc {
+    const float* rd;         // forward: the rows [B,H,W,rows,n]; backward: the upstream gradient of the tensor the rows' taps went to
+    float* wr;               // forward: the tensor the taps go to; backward: the gradient accumulator of the rows
+    int n, rows;             // row length; rows per pixel (C, or 1 for a correlation level)
+    int row0;                // index of the source's first row in a pixel's row list (ascending over the sources)
+    int ch0, nch;            // first channel of the source in its tensor; the tensor's channel count (NCHW) / channel stride (channels-last)
+    int pad_from;            // channels-last: the source that ends its tensor zero-fills channels pad_from .. nch - 1 (others: pad_from = nch)
+    float scale;             // 1, 1/2, 1/4, 1/8
+    int corr;                // 0: x = d * scale (geometry rows), 1: x = cx * scale - d * scale (correlation rows)
+};
+constexpr int MR_MAX_SRC = 10;                                           // 2 * levels + 2, levels <= 4
+struct MultiLookupArgs {
+    LookupSrc src[MR_MAX_SRC];
+    const float* disp; const float* coords;
+    int nsrc, rows_per_px, B, H, W, radius;
+};
+// the source of row j of a pixel.  The loop index is uniform, so the descriptors stay scalar loads from the kernel arguments and a lane picks
+// its own by selects (indexing src[] by a per-lane value would put the whole list into scratch memory)
+__device__ __forceinline__ LookupSrc src_of_row(const MultiLookupArgs& p, int j) {
+    LookupSrc s = p.src[0];
 #pragma unroll
-    for (int q = -2; q <= 1; ++q) {                                      // taps e - 2 .. e + 1 of this row, ascending
-        const int src = (lane + q) & 63;
-        const int xs = __shfl(x0, src);
-        const float a0 = __shfl(t0, src), a1 = __shfl(t1, src);
-        const bool on = e + q >= 0 && e + q < taps;                      // (then lane + q is a lane of this row)
-        if (on && xs == j) { v += a0; hit = true; }
-        if (on && xs + 1 == j) { v += a1; hit = true; }
+    for (int q = 1; q < MR_MAX_SRC; ++q)
+        if (q < p.nsrc && j >= p.src[q].row0) s = p.src[q];
+    return s;
+}
+__device__ __forceinline__ float src_pos(const LookupSrc& s, float d, float cx) {
+    return s.corr ? cx * s.scale - d * s.scale : d * s.scale;
+}
+
+// NCHW: one thread per (row, pixel), consecutive threads on consecutive pixels of one row (geo_lookup_rows_kernel)
+__global__ __launch_bounds__(256) void geo_lookup_mr_rows_kernel(const MultiLookupArgs p) {
+    const long long HW = (long long)p.H * p.W, npix = (long long)p.B * HW;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= npix * p.rows_per_px) return;
+    const int j = (int)(t / npix);                                  // row (uniform over a workgroup unless it straddles a row boundary)
+    const long long i = t - (long long)j * npix;                    // pixel
+    const long long b = i / HW, hw = i - b * HW;
+    const LookupSrc s = src_of_row(p, j);
+    const int c = j - s.row0;
+    const int taps = 2 * p.radius + 1;
+    const float x = src_pos(s, p.disp[i], p.coords[i]);
+    const float* row = s.rd + ((size_t)i * s.rows + c) * s.n;
+    float* o = s.wr + ((size_t)b * s.nch + s.ch0 + (size_t)c * taps) * HW + hw;
+    for (int k = 0; k < taps; ++k) {
+        const float dx = (float)(k - p.radius);
+        o[(size_t)k * HW] = sample_row(row, s.n, tap_of(s.corr ? x + dx : dx + x, s.n));       // operand order of igevpp/geometry.py:43,49,57 / :65
     }
-    if (!row_on || !hit || j < 0 || j >= n) return;
-    float* dst = geo ? p.dgeo[l] + ((size_t)i * p.C + c) * n + j : p.dcorr[l] + (size_t)i * n + j;
-    *dst += v;
+}
+
+// channels-last: one thread per (pixel, row), 2r + 1 contiguous channels of the row's tensor per thread (geo_lookup_nhwc_kernel)
+template <int TAPS>
+__global__ __launch_bounds__(256) void geo_lookup_mr_nhwc_kernel(const MultiLookupArgs p) {
+    const unsigned npix = (unsigned)p.B * p.H * p.W;                // host: B*H*W*rows < 2^31
+    const unsigned t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= npix * (unsigned)p.rows_per_px) return;
+    const unsigned i = t / (unsigned)p.rows_per_px;
+    const int j = (int)(t - i * (unsigned)p.rows_per_px);
+    const LookupSrc s = src_of_row(p, j);
+    const int c = j - s.row0;
+    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
+    const float x = src_pos(s, p.disp[i], p.coords[i]);
+    float* px = s.wr + (size_t)i * s.nch;
+    row_taps_cl<TAPS>(s.rd + ((size_t)i * s.rows + c) * s.n, s.n, x, s.corr != 0, p.radius, px + s.ch0 + c * taps);
+    if (c == s.rows - 1)
+        for (int k = s.pad_from; k < s.nch; ++k) px[k] = 0.f;
+}
+
+// accumulating backward with respect to every source: a row takes 2r + 3 lanes of a wave (geo_lookup_bwd_acc_kernel, see the comment there)
+template <int TAPS>
+__global__ __launch_bounds__(256) void geo_lookup_mr_bwd_acc_kernel(const MultiLookupArgs p) {
+    const unsigned HW = (unsigned)p.H * p.W;
+    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
+    const int G = taps + 2;                                              // <= 64 (host)
+    const int rpw = 64 / G;                                              // rows per wave
+    const unsigned nrows = (unsigned)p.B * HW * (unsigned)p.rows_per_px; // host: < 2^31
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);          // host: waves * rpw < 2^32
+    const int rw = lane / G, e = lane - rw * G;
+    const unsigned R = wave * (unsigned)rpw + rw;
+    const bool row_on = rw < rpw && R < nrows;                           // (no early return: every lane takes part in the shuffles)
+    const unsigned Rc = row_on ? R : 0u;
+    const unsigned i = Rc / (unsigned)p.rows_per_px;                     // pixel
+    const int j = (int)(Rc - i * (unsigned)p.rows_per_px);
+    const LookupSrc s = src_of_row(p, j);
+    const int c = j - s.row0;
+    const unsigned b = i / HW, hw = i - b * HW;
+    const float x = src_pos(s, p.disp[i], p.coords[i]);
+    const float* o = s.rd + ((size_t)b * s.nch + s.ch0 + (size_t)c * taps) * HW + hw;
+    acc_row_window(taps, lane, e, row_on, x, s.n, o, HW, [&](int pos) { return s.wr + ((size_t)i * s.rows + c) * s.n + pos; });
 }
 
 }  // namespace osa
@@ -591,4 +704,100 @@ extern "C" int osa_geo_lookup_f32(const float* const* geo_levels, const float* c
     }
     OSA_LAUNCH_CHECK("geo_lookup");
     return 0;
+}
+
+// ---- multi-range lookup (IGEV++): the three entry points share one argument check and one source list
+namespace {
+enum { MR_NCHW = 0, MR_NHWC = 1, MR_BWD = 2 };
+// SrcT / OutT: const float / float in the forward calls (rows read, tensors written), float / const float in the backward (rows accumulated
+// into, upstream gradients read).  t[4] = geo_feat0, geo_feat1, geo_feat2, init_corr (or their gradients); cs = their channel strides (MR_NHWC).
+template <class SrcT, class OutT>
+int mr_launch(int form, const char* who, SrcT* const* g0, SrcT* const* co, const int* g0_len, const int* co_len, int levels,
+              SrcT* v1, int n1, SrcT* v2, int n2, const float* disp, const float* coords_x, OutT* const t[4], const int* cs,
+              int B, int H, int W, int C, int radius, void* stream) {
+    OSA_REQUIRE(g0 && co && g0_len && co_len && v1 && v2 && disp && coords_x && t[0] && t[1] && t[2] && t[3], "%s: NULL pointer", who);
+    OSA_REQUIRE(levels >= 1 && levels <= 4, "%s: %d levels unsupported (1..4)", who, levels);
+    OSA_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && radius >= 0, "%s: bad dims", who);
+    for (int l = 0; l < levels; ++l)
+        OSA_REQUIRE(g0[l] && co[l] && g0_len[l] > 0 && co_len[l] > 0, "%s: level %d missing", who, l);
+    OSA_REQUIRE(n1 > 0 && n2 > 0, "%s: volume 1 / 2 of length %d / %d", who, n1, n2);
+    const int taps = 2 * radius + 1;
+    const int count[4] = {levels * C * taps, C * taps, C * taps, levels * taps};
+    if (form == MR_NHWC)
+        for (int q = 0; q < 4; ++q) OSA_REQUIRE(cs[q] >= count[q], "%s: channel stride %d < %d channels (tensor %d)", who, cs[q], count[q], q);
+    if (form == MR_BWD) {
+        OSA_REQUIRE(radius <= 30, "%s: radius %d: a row's window of 2r + 3 positions has to fit a wave", who, radius);
+        for (int l = 0; l < levels; ++l) OSA_REQUIRE(g0_len[l] <= (1 << 19) && co_len[l] <= (1 << 19), "%s: level %d longer than 2^19", who, l);
+        OSA_REQUIRE(n1 <= (1 << 19) && n2 <= (1 << 19), "%s: volume 1 / 2 longer than 2^19", who);
+    }
+    MultiLookupArgs a;
+    memset(&a, 0, sizeof(a));
+    int row0 = 0;
+    auto put = [&](SrcT* rows, int n, int nrows, int tensor, int ch0, float scale, int corr, bool ends_tensor) {
+        LookupSrc& s = a.src[a.nsrc++];
+        if constexpr (std::is_const_v<SrcT>) { s.rd = rows; s.wr = t[tensor]; } else { s.rd = t[tensor]; s.wr = rows; }
+        s.n = n; s.rows = nrows; s.row0 = row0; s.ch0 = ch0; s.scale = scale; s.corr = corr;
+        s.nch = form == MR_NHWC ? cs[tensor] : count[tensor];
+        s.pad_from = ends_tensor ? count[tensor] : s.nch;
+        row0 += nrows;
+    };
+    for (int l = 0; l < levels; ++l) put(g0[l], g0_len[l], C, 0, l * C * taps, 1.f / (float)(1 << l), 0, l == levels - 1);   // dx + disp / 2^l
+    put(v1, n1, C, 1, 0, 0.5f, 0, true);                                                                                  // dx + disp / 2
+    put(v2, n2, C, 2, 0, 0.25f, 0, true);                                                                                 // dx + disp / 4
+    for (int l = 0; l < levels; ++l) put(co[l], co_len[l], 1, 3, l * taps, 1.f / (float)(1 << l), 1, l == levels - 1);       // coords / 2^l - disp / 2^l + dx
+    a.rows_per_px = row0;
+    a.disp = disp; a.coords = coords_x; a.B = B; a.H = H; a.W = W; a.radius = radius;
+    const long long total = (long long)B * H * W * row0;                   // (pixel, row) pairs
+    OSA_REQUIRE(total < (1ll << 31), "%s: more than 2^31 (pixel, row) pairs", who);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (form == MR_NCHW) {
+        hipLaunchKernelGGL(geo_lookup_mr_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    } else if (form == MR_NHWC) {
+        if (radius == 4) hipLaunchKernelGGL(geo_lookup_mr_nhwc_kernel<9>, grid, dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(geo_lookup_mr_nhwc_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    } else {
+        const int rpw = 64 / (taps + 2);                                    // rows per wave
+        const long long waves = (total + rpw - 1) / rpw;
+        const dim3 bgrid((unsigned)((waves + 3) / 4));
+        if (radius == 4) hipLaunchKernelGGL(geo_lookup_mr_bwd_acc_kernel<9>, bgrid, dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(geo_lookup_mr_bwd_acc_kernel<0>, bgrid, dim3(256), 0, (hipStream_t)stream, a);
+    }
+    OSA_LAUNCH_CHECK(who);
+    return 0;
+}
+}  // namespace
+
+extern "C" int osa_geo_lookup_mr_f32(const float* const* geo0_levels, const float* const* corr_levels,
+                                     const int* geo0_len, const int* corr_len, int levels,
+                                     const float* geo1, int geo1_len, const float* geo2, int geo2_len,
+                                     const float* disp, const float* coords_x,
+                                     float* geo_feat0, float* geo_feat1, float* geo_feat2, float* init_corr,
+                                     int B, int H, int W, int C, int radius, void* stream) {
+    float* const t[4] = {geo_feat0, geo_feat1, geo_feat2, init_corr};
+    return mr_launch<const float, float>(MR_NCHW, "geo_lookup_mr", geo0_levels, corr_levels, geo0_len, corr_len, levels, geo1, geo1_len, geo2, geo2_len,
+                                         disp, coords_x, t, nullptr, B, H, W, C, radius, stream);
+}
+
+extern "C" int osa_geo_lookup_mr_nhwc_f32(const float* const* geo0_levels, const float* const* corr_levels,
+                                          const int* geo0_len, const int* corr_len, int levels,
+                                          const float* geo1, int geo1_len, const float* geo2, int geo2_len,
+                                          const float* disp, const float* coords_x,
+                                          float* geo_feat0, float* geo_feat1, float* geo_feat2, float* init_corr,
+                                          int cs0, int cs1, int cs2, int cs_corr,
+                                          int B, int H, int W, int C, int radius, void* stream) {
+    float* const t[4] = {geo_feat0, geo_feat1, geo_feat2, init_corr};
+    const int cs[4] = {cs0, cs1, cs2, cs_corr};
+    return mr_launch<const float, float>(MR_NHWC, "geo_lookup_mr_nhwc", geo0_levels, corr_levels, geo0_len, corr_len, levels, geo1, geo1_len, geo2, geo2_len,
+                                         disp, coords_x, t, cs, B, H, W, C, radius, stream);
+}
+
+extern "C" int osa_geo_lookup_mr_bwd_acc_f32(float* const* dgeo0_levels, float* const* dcorr_levels,
+                                             const int* geo0_len, const int* corr_len, int levels,
+                                             float* dgeo1, int geo1_len, float* dgeo2, int geo2_len,
+                                             const float* disp, const float* coords_x,
+                                             const float* dfeat0, const float* dfeat1, const float* dfeat2, const float* dcorr_out,
+                                             int B, int H, int W, int C, int radius, void* stream) {
+    const float* const t[4] = {dfeat0, dfeat1, dfeat2, dcorr_out};
+    return mr_launch<float, const float>(MR_BWD, "geo_lookup_mr_bwd_acc", dgeo0_levels, dcorr_levels, geo0_len, corr_len, levels, dgeo1, geo1_len, dgeo2, geo2_len,
+                                         disp, coords_x, t, nullptr, B, H, W, C, radius, stream);
 }

@@ -635,6 +635,42 @@ void geo_lookup_nhwc(at::TensorList levels, const at::Tensor& disp, const at::Te
                                      cur_stream()));
 }
 
+// multi-range lookup of IGEV++ (igevpp/geometry.py:6-87).  `sources` = the levels of volume 0, volume 1, volume 2, the corr levels (2 L + 2 row
+// tensors, the last axis the row); `outs` = geo_feat0, geo_feat1, geo_feat2, init_corr.  form 0: NCHW outs, 1: channels-last outs with the channel
+// strides `cs`, 2: `sources` are the gradient accumulators and `outs` the upstream gradients of the NCHW outs.
+static void geo_lookup_mr_any(int form, const char* who, at::TensorList sources, const at::Tensor& disp, const at::Tensor& coords_x, at::TensorList outs, at::IntArrayRef cs,
+                              int B, int H, int W, int64_t C, int64_t radius) {
+    const size_t L = sources.size() >= 2 ? (sources.size() - 2) / 2 : 0;
+    TORCH_CHECK(L >= 1 && L <= 4 && sources.size() == 2 * L + 2 && outs.size() == 4 && (form != 1 || cs.size() == 4), who,
+                ": sources = volume-0 levels + volume 1 + volume 2 + corr levels (1..4 levels), four outs");
+    gpu_f32(disp, "disp"); gpu_f32(coords_x, "coords_x");
+    float* sp[10]; int sl[10]; float* op[4];
+    for (size_t q = 0; q < 2 * L + 2; ++q) { sp[q] = gpu_f32(sources[q], "source").data_ptr<float>(); sl[q] = (int)sources[q].size(-1); }
+    for (size_t q = 0; q < 4; ++q) op[q] = gpu_f32(outs[q], "out").data_ptr<float>();
+    float** g0 = sp; float** co = sp + L + 2;
+    const int* g0l = sl; const int* col = sl + L + 2;
+    if (form == 0)
+        OSA_CALL(osa_geo_lookup_mr_f32(g0, co, g0l, col, (int)L, sp[L], sl[L], sp[L + 1], sl[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
+                                       B, H, W, (int)C, (int)radius, cur_stream()));
+    else if (form == 1)
+        OSA_CALL(osa_geo_lookup_mr_nhwc_f32(g0, co, g0l, col, (int)L, sp[L], sl[L], sp[L + 1], sl[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
+                                            (int)cs[0], (int)cs[1], (int)cs[2], (int)cs[3], B, H, W, (int)C, (int)radius, cur_stream()));
+    else
+        OSA_CALL(osa_geo_lookup_mr_bwd_acc_f32(g0, co, g0l, col, (int)L, sp[L], sl[L], sp[L + 1], sl[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
+                                               B, H, W, (int)C, (int)radius, cur_stream()));
+}
+void geo_lookup_mr(at::TensorList sources, const at::Tensor& disp, const at::Tensor& coords_x, at::TensorList outs, int64_t C, int64_t radius) {
+    geo_lookup_mr_any(0, "geo_lookup_mr", sources, disp, coords_x, outs, {}, (int)disp.size(0), (int)disp.size(1), (int)disp.size(2), C, radius);
+}
+void geo_lookup_mr_nhwc(at::TensorList sources, const at::Tensor& disp, const at::Tensor& coords_x, at::TensorList outs, at::IntArrayRef out_cs, at::IntArrayRef bhw,
+                        int64_t C, int64_t radius) {
+    TORCH_CHECK(bhw.size() == 3, "geo_lookup_mr_nhwc: bhw = [B, H, W]");
+    geo_lookup_mr_any(1, "geo_lookup_mr_nhwc", sources, disp, coords_x, outs, out_cs, (int)bhw[0], (int)bhw[1], (int)bhw[2], C, radius);
+}
+void geo_lookup_mr_bwd_acc(at::TensorList dsources, const at::Tensor& disp, const at::Tensor& coords_x, at::TensorList douts, int64_t C, int64_t radius) {
+    geo_lookup_mr_any(2, "geo_lookup_mr_bwd_acc", dsources, disp, coords_x, douts, {}, (int)disp.size(0), (int)disp.size(1), (int)disp.size(2), C, radius);
+}
+
 // pyramid construction (igev/geometry.py:8-31): all-pairs correlation, volume -> per-pixel rows, row-wise average pooling
 void allpairs_corr(const at::Tensor& f1, const at::Tensor& f2, at::Tensor corr) {
     gpu_f32(f1, "fmap1"); gpu_f32(f2, "fmap2"); gpu_f32(corr, "corr");
@@ -1146,6 +1182,9 @@ TORCH_LIBRARY(osa_native, m) {
     m.def("disp_update(Tensor(a!) disp, Tensor? delta, int delta_cs, Tensor(b!) disp4, Tensor(c!) slot, int slot_off, int slot_cs, int npix, Tensor(d!)? disp4_meta, "
           "Tensor(e!)? slot_meta) -> ()");
     m.def("geo_lookup_nhwc(Tensor[] levels, Tensor disp, Tensor coords_x, Tensor(a!) out, int out_cs, int[] bhw, int C, int radius) -> ()");
+    m.def("geo_lookup_mr(Tensor[] sources, Tensor disp, Tensor coords_x, Tensor(a!)[] outs, int C, int radius) -> ()");
+    m.def("geo_lookup_mr_nhwc(Tensor[] sources, Tensor disp, Tensor coords_x, Tensor(a!)[] outs, int[] out_cs, int[] bhw, int C, int radius) -> ()");
+    m.def("geo_lookup_mr_bwd_acc(Tensor(a!)[] dsources, Tensor disp, Tensor coords_x, Tensor[] douts, int C, int radius) -> ()");
     m.def("allpairs_corr(Tensor fmap1, Tensor fmap2, Tensor(a!) corr) -> ()");
     m.def("geo_rows(Tensor volume, Tensor(a!) rows, int C) -> ()");
     m.def("avgpool_rows(Tensor x, Tensor(a!) y) -> ()");
@@ -1204,6 +1243,9 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
     m.impl("resample_nhwc", &resample_nhwc);
     m.impl("disp_update", &disp_update);
     m.impl("geo_lookup_nhwc", &geo_lookup_nhwc);
+    m.impl("geo_lookup_mr", &geo_lookup_mr);
+    m.impl("geo_lookup_mr_nhwc", &geo_lookup_mr_nhwc);
+    m.impl("geo_lookup_mr_bwd_acc", &geo_lookup_mr_bwd_acc);
     m.impl("allpairs_corr", &allpairs_corr);
     m.impl("geo_rows", &geo_rows);
     m.impl("avgpool_rows", &avgpool_rows);
@@ -1249,7 +1291,7 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
     m.impl("context_upsample_logits_bwd", &context_upsample_logits_bwd_meta);
     for (const char* name : {"conv_ndhwc", "to_cl", "to_ncdhw", "conv_pack", "deconv_pack", "gru_gates_rz_fwd", "gru_gates_rz_bwd", "gru_gates_q_fwd", "gru_gates_q_bwd",
                              "geo_lookup", "geo_lookup_bwd", "geo_lookup_bwd_acc", "build_volume", "deconv_redir", "small_co_conv", "dwconv2d", "dwconv2d_f16io", "gru_combine", "resample_nhwc", "disp_update",
-                             "geo_lookup_nhwc", "allpairs_corr", "geo_rows", "avgpool_rows", "weight_pack", "cat_fms", "pair_volume", "instnorm_nhwc", "preprocess_pair",
+                             "geo_lookup_nhwc", "geo_lookup_mr", "geo_lookup_mr_nhwc", "geo_lookup_mr_bwd_acc", "allpairs_corr", "geo_rows", "avgpool_rows", "weight_pack", "cat_fms", "pair_volume", "instnorm_nhwc", "preprocess_pair",
                              "amax_into"})
         m.impl(name, torch::CppFunction::makeFromBoxedFunction<&noop_boxed>());
 }

@@ -34,11 +34,6 @@ def chains(precision: str) -> bool:
     return precision in ("f16x3", "f16")
 
 
-def chain_ok(layer) -> bool:
-    """`layer`'s output can be written in its mode's chain format: every 16-channel chunk complete (f16x3) / 8-channel row complete (f16)"""
-    return (layer.precision == "f16x3" and layer.Co % 16 == 0) or (layer.precision == "f16" and layer.Co % 8 == 0)
-
-
 from .ranges import META_FLOATS, new_meta, meta_of, input_meta, ensure_meta, fold_amax, attach_meta   # noqa: E402,F401  (f16x3 operand ranges)
 
 

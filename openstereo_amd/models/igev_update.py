@@ -39,14 +39,6 @@ def _nhwc(x):
     return x.permute(0, 2, 3, 4, 1).reshape(B, H, W, C)
 
 
-def _as_cl(t4):
-    """4-D logical NCHW tensor (any strides) -> engine tensor, without a copy when it already is NHWC."""
-    B, C, H, W = t4.shape
-    if C % 4 == 0 and t4.dtype == torch.float32 and t4.stride() == (H * W * C, 1, W * C, C):
-        return t4.unsqueeze(2)
-    return nchw_to_cl(t4)
-
-
 def _fold_meta(dst, src):
     """dst's range block (f16x3 chains) must cover values copied / resampled from src: slot-wise maximum, one tiny kernel."""
     m = meta_of(dst)
@@ -79,9 +71,6 @@ class _GruLevel:
         C = part.shape[1]
         self.T[:, self.hd + off:self.hd + off + C] = part
         _fold_meta(self.T, part)
-
-    def h_out(self):
-        return self.T                                   # consumers read channels [0, hd) (PackedConv3d takes Cs >= Ci; cl_to_nchw slices)
 
 
 def _resample_into(kind, src, C, dst, off):
