@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 10
+#define OSA_ABI_VERSION 11
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -511,6 +511,27 @@ int osa_build_volume_bwd_f32(const float* dvol, const float* left, const float* 
                              int B, int C, int H, int W, int maxdisp, int num_groups,
                              int concat, int mask_left_concat, int vol_channels, int c_off,
                              void* stream);
+/* IGEV++ multi-range cost volumes (igevpp_stereo.py:182-186), ABI 11.  With gwc = the group-wise correlation volume of left / right
+ * [B,C,H,W] (NCHW) over maxdisp planes, ONE launch writes
+ *   v0 [B,8,s_range,H,W]      = gwc[:, :, :s_range]   (bit-identical to osa_build_volume_f32's planes)
+ *   v1 [B,8,m_range/k0,H,W]   = Conv3d(8, 8, (k0,1,1), stride (k0,1,1), no bias)(gwc[:, :, :m_range]), weight patch0 [8,8,k0]
+ *   v2 [B,8,maxdisp/k1,H,W]   = the same with patch1 [8,8,k1] over all planes
+ * without the full-range volume ever reaching memory.  layout: OSA_NCDHW or OSA_NDHWC, for all three outputs.
+ * Supported: num_groups == out_channels == 8, k0, k1 in {2, 4}, 0 < s_range <= m_range <= maxdisp, m_range % k0 == 0, maxdisp % k1 == 0,
+ * any C % 8 == 0, any W. */
+int osa_mr_volume_f32(const float* left, const float* right, const float* patch0, const float* patch1,
+                      float* v0, float* v1, float* v2, int layout,
+                      int B, int C, int H, int W, int num_groups, int out_channels, int maxdisp, int s_range, int m_range, int k0, int k1,
+                      void* stream);
+/* Its backward: dleft / dright [B,C,H,W] and dpatch0 / dpatch1 from the output gradients dv0 / dv1 / dv2 (in `layout`; any of them may be
+ * NULL = zero).  The group correlations are recomputed from the features; no atomics, two runs give the same bits.  `workspace`: at least
+ * osa_mr_volume_bwd_workspace_bytes(B, H, W, maxdisp) bytes of device memory (per-workgroup partial sums of the weight gradients). */
+size_t osa_mr_volume_bwd_workspace_bytes(int B, int H, int W, int maxdisp);
+int osa_mr_volume_bwd_ws_f32(const float* dv0, const float* dv1, const float* dv2, int layout,
+                             const float* left, const float* right, const float* patch0, const float* patch1,
+                             float* dleft, float* dright, float* dpatch0, float* dpatch1,
+                             int B, int C, int H, int W, int num_groups, int out_channels, int maxdisp, int s_range, int m_range, int k0, int k1,
+                             void* workspace, size_t workspace_bytes, void* stream);
 /* dprob[b,d,h,w] = d * dout[b,h,w] */
 int osa_softargmin_bwd_f32(const float* dout, float* dprob, int B, int D, int H, int W, void* stream);
 /* dcost = softmax(cost) * (d - disp) * dout */

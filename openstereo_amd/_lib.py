@@ -46,10 +46,8 @@ SIGNATURES = {
     "osa_abi_version": (c_i, []),
     "osa_last_error": (C.c_char_p, []),
     "osa_target_arch": (C.c_char_p, []),
-    "osa_build_volume_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_i, c_fp, c_i, c_i, c_i,
-                                   c_i, c_i, c_i, c_i, c_i, c_fp, c_st]),
-    "osa_build_volume_nhwc_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp, c_i, c_i,
-                                        c_i, c_i, c_i, c_i, c_i, c_fp, c_st]),
+    "osa_build_volume_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_i, c_fp] + [c_i] * 8 + [c_fp, c_st]),
+    "osa_build_volume_nhwc_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp] + [c_i] * 7 + [c_fp, c_st]),
     "osa_corr_volume_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_ncdhw_to_ndhwc_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_ll, c_i, c_i, c_st]),
     "osa_ndhwc_to_ncdhw_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_ll, c_i, c_i, c_st]),
@@ -57,56 +55,24 @@ SIGNATURES = {
     "osa_conv3d_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_deconv3d_packed_floats": (C.c_size_t, [c_i, c_i, c_i]),
     "osa_deconv3d_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_conv3d_ndhwc_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                   c_i, c_i, c_i, c_i, c_i, c_i,
-                                   c_i, c_i, c_i,
-                                   c_i, c_i, c_i, c_i,
-                                   c_i, c_i, c_i,
-                                   c_i, c_i, c_i,
-                                   c_fp, c_i,
-                                   c_i, c_f, c_st]),
-    "osa_deconv3d_ndhwc_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                     c_i, c_i, c_i, c_i, c_i, c_i,
-                                     c_i, c_i, c_i,
-                                     c_i, c_i, c_i,
-                                     c_fp, c_i,
-                                     c_i, c_f, c_st]),
+    "osa_conv3d_ndhwc_f32": (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_st]),
+    "osa_deconv3d_ndhwc_f32": (c_i, [c_fp] * 6 + [c_i] * 12 + [c_fp, c_i, c_i, c_f, c_st]),
     "osa_conv3d_pack_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_st]),
     "osa_deconv3d_pack_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_st]),
-    "osa_conv3d_ndhwc_f16x3": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                     c_i, c_i, c_i, c_i, c_i, c_i,
-                                     c_i, c_i, c_i,
-                                     c_i, c_i, c_i, c_i,
-                                     c_i, c_i, c_i,
-                                     c_i, c_i, c_i,
-                                     c_fp, c_i,
-                                     c_i, c_f, c_f, c_rng, c_st]),
-    "osa_deconv3d_ndhwc_f16x3": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                       c_i, c_i, c_i, c_i, c_i, c_i,
-                                       c_i, c_i, c_i,
-                                       c_i, c_i, c_i,
-                                       c_fp, c_i,
-                                       c_i, c_f, c_f, c_rng, c_st]),
+    "osa_conv3d_ndhwc_f16x3": (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_f, c_rng, c_st]),
+    "osa_deconv3d_ndhwc_f16x3": (c_i, [c_fp] * 6 + [c_i] * 12 + [c_fp, c_i, c_i, c_f, c_f, c_rng, c_st]),
     "osa_conv3d_pack_ex": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_st]),
     "osa_pair_volume_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_conv3d_wgrad_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                   c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_conv3d_wgrad_f32": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 22 + [c_st]),
     "osa_conv3d_wgrad_workspace_bytes": (C.c_size_t, [c_i] * 20),
-    "osa_conv3d_wgrad_ws_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                      c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, C.c_size_t, c_st]),
+    "osa_conv3d_wgrad_ws_f32": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 22 + [c_fp, C.c_size_t, c_st]),
     "osa_conv3d_wgrad_f16x3_workspace_bytes": (C.c_size_t, [c_i] * 20),
-    "osa_conv3d_wgrad_ws_f16x3": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                        c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, C.c_size_t, c_st]),
-    "osa_conv3d_wgrad_ws_f16": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                      c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp, C.c_size_t, c_st]),
-    "osa_conv3d_small_co_ndhwc_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp,
-                                            c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                            c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_conv3d_wgrad_ws_f16x3": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 22 + [c_fp, c_fp, c_fp, C.c_size_t, c_st]),
+    "osa_conv3d_wgrad_ws_f16": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 22 + [c_fp, c_fp, c_i, c_i, c_fp, C.c_size_t, c_st]),
+    "osa_conv3d_small_co_ndhwc_f32": (c_i, [c_fp] * 5 + [c_i] * 14 + [c_st]),
     "osa_conv3d_small_co_packed_floats": (C.c_size_t, [c_i, c_i, c_i, c_i, c_i]),
     "osa_conv3d_small_co_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_conv3d_small_co_packed_ndhwc_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp,
-                                            c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                            c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    "osa_conv3d_small_co_packed_ndhwc_f32": (c_i, [c_fp] * 5 + [c_i] * 14 + [c_st]),
     "osa_build_volume_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_softargmin_bwd_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_softmax_softargmin_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
@@ -114,34 +80,15 @@ SIGNATURES = {
     "osa_amax_f32": (c_i, [c_fp, C.c_longlong, c_fp, c_st]),
     "osa_upsample_softargmin_bwd_workspace_bytes": (C.c_size_t, [c_i] * 4),
     "osa_upsample_softargmin_bwd_ws_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, C.c_size_t, c_st]),
-    "osa_deconv3d_redir_ndhwc_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp,
-                                           c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                           c_i, c_i, c_i,
-                                           c_fp, c_i, c_i, c_fp, c_fp, c_fp,
-                                           c_i, c_f, c_st]),
-    "osa_deconv3d_redir_ndhwc_f16x3": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp,
-                                             c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                             c_i, c_i, c_i,
-                                             c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_f,
-                                             c_i, c_f, c_f, c_rng, c_st]),
+    "osa_deconv3d_redir_ndhwc_f32": (c_i, [c_fp] * 5 + [c_i] * 11 + [c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_f, c_st]),
+    "osa_deconv3d_redir_ndhwc_f16x3": (c_i, [c_fp] * 5 + [c_i] * 11 + [c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_f, c_i, c_f, c_f, c_rng, c_st]),
     "osa_deconv2d_packed_floats": (C.c_size_t, [c_i, c_i, c_i]),
     "osa_deconv2d_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_deconv2d_pack_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_st]),
-    "osa_deconv2d_nhwc_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                    c_i, c_i, c_i, c_i, c_i,
-                                    c_i, c_i, c_i,
-                                    c_i, c_i, c_i,
-                                    c_fp, c_i, c_i, c_f, c_st]),
-    "osa_deconv2d_nhwc_f16x3": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                      c_i, c_i, c_i, c_i, c_i,
-                                      c_i, c_i, c_i,
-                                      c_i, c_i, c_i,
-                                      c_fp, c_i, c_i, c_f, c_f, c_rng, c_st]),
+    "osa_deconv2d_nhwc_f32": (c_i, [c_fp] * 6 + [c_i] * 11 + [c_fp, c_i, c_i, c_f, c_st]),
+    "osa_deconv2d_nhwc_f16x3": (c_i, [c_fp] * 6 + [c_i] * 11 + [c_fp, c_i, c_i, c_f, c_f, c_rng, c_st]),
     "osa_dwconv2d_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_st]),
-    "osa_dwconv2d_nhwc_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                    c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                    c_i, c_i, c_i, c_i, c_i, c_i, c_i,
-                                    c_i, c_fp, c_st]),
+    "osa_dwconv2d_nhwc_f32": (c_i, [c_fp] * 6 + [c_i] * 15 + [c_fp, c_st]),
     "osa_dwconv2d_nhwc_f16io": (c_i, [c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_i] + [c_i] * 11 + [c_i, c_fp, c_st]),
     "osa_gru_combine_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_ll, c_i, c_i, c_i, c_i, c_i, c_fp, c_st]),
     "osa_gru_gates_rz_fwd": (c_i, [c_ref, c_fp, c_fp, c_ref, c_ref, c_ref, c_ref, c_ref, c_ll, c_i, c_st]),
@@ -172,25 +119,9 @@ SIGNATURES = {
     "osa_conv3d_pack_f16": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_deconv3d_pack_f16": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_deconv2d_pack_f16": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_conv3d_ndhwc_f16": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                   c_i, c_i, c_i, c_i, c_i, c_i,
-                                   c_i, c_i, c_i,
-                                   c_i, c_i, c_i, c_i,
-                                   c_i, c_i, c_i,
-                                   c_i, c_i, c_i,
-                                   c_fp, c_i,
-                                   c_i, c_f, c_st]),
-    "osa_deconv3d_ndhwc_f16": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                     c_i, c_i, c_i, c_i, c_i, c_i,
-                                     c_i, c_i, c_i,
-                                     c_i, c_i, c_i,
-                                     c_fp, c_i,
-                                     c_i, c_f, c_st]),
-    "osa_deconv2d_nhwc_f16": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                    c_i, c_i, c_i, c_i, c_i,
-                                    c_i, c_i, c_i,
-                                    c_i, c_i, c_i,
-                                    c_fp, c_i, c_i, c_f, c_st]),
+    "osa_conv3d_ndhwc_f16": (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_st]),
+    "osa_deconv3d_ndhwc_f16": (c_i, [c_fp] * 6 + [c_i] * 12 + [c_fp, c_i, c_i, c_f, c_st]),
+    "osa_deconv2d_nhwc_f16": (c_i, [c_fp] * 6 + [c_i] * 11 + [c_fp, c_i, c_i, c_f, c_st]),
     "osa_instnorm_workspace_floats": (C.c_size_t, [c_i, c_ll, c_i]),
     "osa_instnorm_nhwc_f32": (c_i, [c_fp, c_fp, c_i, c_ll, c_i, c_i, c_i, c_f, c_i, c_f, c_fp, c_fp, c_st]),
     "osa_conv3d_wgrad_ws_multi": (c_i, [c_i, c_fp, c_fp, c_i, c_fp] + [c_i] * 22 + [c_fp, c_fp, c_i, c_i, c_fp, C.c_size_t, c_st]),
@@ -208,8 +139,7 @@ SIGNATURES = {
     "osa_volume_walk_step": (c_i, [c_i]),
     "osa_volume_walk_launches": (c_ll, []),
     "osa_build_volume_nhwc_split_eligible": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
-    "osa_build_volume_nhwc_split_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp, c_i, c_i,
-                                                c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_fp, c_st]),
+    "osa_build_volume_nhwc_split_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp] + [c_i] * 7 + [c_fp, c_fp, c_fp, c_st]),
     "osa_softargmin_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_softmax_softargmin_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_upsample_softargmin_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
@@ -219,6 +149,9 @@ SIGNATURES = {
     "osa_softargmin_var_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_softmax_softargmin_var_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_upsample_softargmin_var_bwd_ws_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, C.c_size_t, c_st]),
+    "osa_mr_volume_f32": (c_i, [c_fp] * 7 + [c_i] * 12 + [c_st]),
+    "osa_mr_volume_bwd_workspace_bytes": (C.c_size_t, [c_i] * 4),
+    "osa_mr_volume_bwd_ws_f32": (c_i, [c_fp] * 3 + [c_i] + [c_fp] * 8 + [c_i] * 11 + [c_fp, C.c_size_t, c_st]),
 }
 
 

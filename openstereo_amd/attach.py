@@ -139,15 +139,13 @@ def _targets():
         ("stereo.modeling.models.gwcnet.gwcnet_disp_processor", "disparity_regression", reg_nokeep),
         ("stereo.modeling.models.psmnet.psmnet_cost_processor", "cat_fms", cat_fms),
         ("stereo.modeling.models.psmnet.psmnet_disp_processor", "FasterSoftArgmin", ops.FasterSoftArgmin),
-        ("stereo.modeling.models.igev.submodule", "build_gwc_volume", build_gwc_volume),
-        ("stereo.modeling.models.igev.submodule", "build_concat_volume", igev_concat),
-        ("stereo.modeling.models.igev.submodule", "disparity_regression", reg_keep),
-        ("stereo.modeling.models.igev.submodule", "context_upsample", context_upsample),
-        ("stereo.modeling.models.igev.igev_stereo", "build_gwc_volume", build_gwc_volume),
-        ("stereo.modeling.models.igev.igev_stereo", "build_concat_volume", igev_concat),
-        ("stereo.modeling.models.igev.igev_stereo", "disparity_regression", reg_keep),
-        ("stereo.modeling.models.igev.igev_stereo", "context_upsample", context_upsample),
-    ]
+        # igevpp/submodule.py:87-97, 147-159, 177-186 (its context_upsample keeps the channel dimension)
+        (M + "igevpp.submodule", "build_gwc_volume", build_gwc_volume),
+        (M + "igevpp.submodule", "disparity_regression", lambda prob, maxdisp, interval: ops.disparity_regression(prob, maxdisp, True, interval)),
+        (M + "igevpp.submodule", "disparity_variance", ops.disparity_variance),
+        (M + "igevpp.submodule", "context_upsample", lambda disp_low, up_weights: context_upsample(disp_low, up_weights).unsqueeze(1)),
+    ] + [(M + "igev." + mod, name, fn) for mod in ("submodule", "igev_stereo") for name, fn in (
+        ("build_gwc_volume", build_gwc_volume), ("build_concat_volume", igev_concat), ("disparity_regression", reg_keep), ("context_upsample", context_upsample))]
 
 
 def stub_reference_packages(ref_root: str):

@@ -58,7 +58,7 @@ def lib_path() -> str:
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "osa_common.h"), os.path.join(CSRC, "conv_kernel.h"), os.path.join(CSRC, "conv_march.h"), os.path.join(CSRC, "conv_march_s2.h"), os.path.join(CSRC, "conv_deconv_walk.h"), os.path.join(CSRC, "conv_inst.h"), os.path.join(CSRC, "conv_inst_impl.h"), os.path.join(CSRC, "conv_cfgs.def"), os.path.join(CSRC, "head_common.h"),
+    headers = [os.path.join(CSRC, "osa_common.h"), os.path.join(CSRC, "conv_kernel.h"), os.path.join(CSRC, "conv_march.h"), os.path.join(CSRC, "conv_march_s2.h"), os.path.join(CSRC, "conv_deconv_walk.h"), os.path.join(CSRC, "conv_inst.h"), os.path.join(CSRC, "conv_inst_impl.h"), os.path.join(CSRC, "conv_cfgs.def"), os.path.join(CSRC, "head_common.h"), os.path.join(CSRC, "mr_volume.h"),
                os.path.join(HERE, "..", "include", "openstereo_amd.h")]
 
     def compile_one(src: str) -> str:

@@ -427,3 +427,192 @@ extern "C" int osa_upsample_softargmin_var_bwd_ws_f32(const float* cost_lowres, 
     return launch_upsample_softargmin_bwd_ws(cost_lowres, dout, dvar, dcost_lowres, B, Dl, Hl, Wl, D, H, W, align_corners,
                                              workspace, workspace_bytes, (hipStream_t)stream);
 }
+
+// ------------------------------------------------------------------ IGEV++ multi-range volumes (mr_volume.h) ----
+// dgwc[g,d] = [d<S] dV0[g,d] + [d<M] sum_o P0[o,g,d%k0] dV1[o,d/k0] + sum_o P1[o,g,d%k1] dV2[o,d/k1] is recomputed wherever it is needed.
+#include "mr_volume.h"
+namespace osa {
+
+// Data gradients, no atomics: a lane owns one pixel of ONE image and CPB channels of one group (blockIdx.y), and walks d.
+// RIGHT = false: dL[c,w] = (1/K) sum_{d<=w} dgwc[g,d,w] R[c,w-d];  RIGHT = true: dR[c,x] = (1/K) sum_{x+d<W} dgwc[g,d,x+d] L[c,x+d].
+template <int CPB, int K0, int K1, bool CL, bool RIGHT>
+__global__ __launch_bounds__(64) void mr_volume_bwd_data_kernel(const MrArgs p) {
+    unsigned bid = blockIdx.x;
+    const int wt = bid % p.nWt; bid /= p.nWt;
+    const int h = bid % p.H, b = bid / p.H;
+    const int px = wt * MR_WT + (int)threadIdx.x;
+    if (px >= p.W) return;
+    const int c0 = blockIdx.y * CPB, g = c0 / p.K;
+    const size_t plane = (size_t)p.H * p.W;
+    const float* F = (RIGHT ? p.L : p.R) + ((size_t)b * p.C + c0) * plane + (size_t)h * p.W;     // the other image's features
+    const int D1 = p.M / K0, D2 = p.D / K1;
+    float w0r[K0][MR_G], w1r[K1][MR_G];                     // this group's patch weights (uniform)
+#pragma unroll
+    for (int o = 0; o < MR_G; ++o) {
+#pragma unroll
+        for (int j = 0; j < K0; ++j) w0r[j][o] = p.P0[(o * MR_G + g) * K0 + j];
+#pragma unroll
+        for (int j = 0; j < K1; ++j) w1r[j][o] = p.P1[(o * MR_G + g) * K1 + j];
+    }
+    float acc[CPB];
+#pragma unroll
+    for (int k = 0; k < CPB; ++k) acc[k] = 0.f;
+    const int dend = RIGHT ? min(p.D, p.W - px) : min(p.D, px + 1);       // the planes at which this pixel is paired
+    for (int d4 = 0; d4 < dend; d4 += 4) {
+#pragma unroll
+        for (int j4 = 0; j4 < 4; ++j4) {                    // d % 4 == j4: the patch taps are compile-time
+            const int d = d4 + j4;
+            if (d < dend) {
+                const int wq = RIGHT ? px + d : px, xo = RIGHT ? px + d : px - d;
+                float dg = 0.f, v[MR_G];
+                if (p.V0 && d < p.S) dg = p.V0[mr_vox<CL>(b, g, d, p.S, h, p.H, wq, p.W)];
+                if (p.V1 && d < p.M) {
+                    mr_load8<CL>(v, p.V1, b, d / K0, D1, h, p.H, wq, p.W);
+#pragma unroll
+                    for (int o = 0; o < MR_G; ++o) dg = fmaf(w0r[j4 % K0][o], v[o], dg);
+                }
+                if (p.V2) {
+                    mr_load8<CL>(v, p.V2, b, d / K1, D2, h, p.H, wq, p.W);
+#pragma unroll
+                    for (int o = 0; o < MR_G; ++o) dg = fmaf(w1r[j4 % K1][o], v[o], dg);
+                }
+#pragma unroll
+                for (int k = 0; k < CPB; ++k) acc[k] = fmaf(dg, F[(size_t)k * plane + xo], acc[k]);
+            }
+        }
+    }
+    float* out = (RIGHT ? p.dR : p.dL) + ((size_t)b * p.C + c0) * plane + (size_t)h * p.W + px;
+    const float Kf = (float)p.K;
+#pragma unroll
+    for (int k = 0; k < CPB; ++k) out[(size_t)k * plane] = acc[k] / Kf;
+}
+
+// Weight gradients, stage 1: dP[o,g,j] = sum dV[o,d',w] gwc[g,k d'+j,w] with gwc recomputed as in the forward.  Four waves share a pixel
+// tile and its ring; wave r walks the planes d = r (mod 4), for which both taps j0 = r % k0 and j1 = r % k1 are fixed, so a lane keeps
+// 64 + 64 partial sums.  They are reduced over the wave in a fixed order and written to ws[chunk][block][r][128]: no atomics.
+template <int KT, int K0, int K1, bool CL>
+__global__ __launch_bounds__(256) void mr_volume_bwd_w_kernel(const MrArgs p) {
+    constexpr int CT = MR_G * KT;
+    __shared__ float ring[KT ? CT * MR_RING : 1];
+    unsigned bid = blockIdx.x;
+    const int wt = bid % p.nWt; bid /= p.nWt;
+    const int h = bid % p.H, b = bid / p.H;
+    const int tid = threadIdx.x, lane = tid & 63, r = tid >> 6, w0 = wt * MR_WT, w = w0 + lane;
+    const bool live = w < p.W;
+    const size_t plane = (size_t)p.H * p.W;
+    const float* Lrow = p.L + (size_t)b * p.C * plane + (size_t)h * p.W;
+    const float* Rrow = p.R + (size_t)b * p.C * plane + (size_t)h * p.W;
+    const float Kf = (float)p.K;
+    const int D1 = p.M / K0, D2 = p.D / K1;
+    const int d0 = blockIdx.y * p.DCH, dend = min(p.D, d0 + p.DCH);
+    float a1[64], a2[64];                                   // [o][g]
+#pragma unroll
+    for (int i = 0; i < 64; ++i) a1[i] = a2[i] = 0.f;
+    if (d0 <= w0 + MR_WT - 1) {                             // (else no pixel of the tile reaches this chunk: its partial sums are zero)
+        float Lr[KT ? CT : 1];
+        if constexpr (KT > 0) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) Lr[c] = live ? Lrow[(size_t)c * plane + w] : 0.f;
+            mr_stage<CT, 256>(ring, Rrow, plane, p.W, w0 - d0 - MR_DS + 1, MR_WT + MR_DS - 1, tid);
+        }
+        __syncthreads();
+        for (int ds = d0; ds < dend; ds += MR_DS) {
+            [[maybe_unused]] float nb[KT ? CT * MR_DS / 256 : 1];
+            const int xn = w0 + 1 - ds - 2 * MR_DS;
+            const bool more = ds + MR_DS < dend;
+            if constexpr (KT > 0) if (more) mr_fetch<CT, 256>(nb, Rrow, plane, p.W, xn, tid);
+#pragma unroll 1
+            for (int d = ds + r; d < min(ds + MR_DS, dend); d += 4) {
+                if (live && w >= d) {                       // (elsewhere gwc is zero)
+                    float c[MR_G], v[MR_G];
+                    mr_gwc<KT>(c, Lr, ring, Lrow, Rrow, plane, p.K, Kf, w, d, live);
+                    if (p.V1 && d < p.M) {
+                        mr_load8<CL>(v, p.V1, b, d / K0, D1, h, p.H, w, p.W);
+#pragma unroll
+                        for (int o = 0; o < MR_G; ++o)
+#pragma unroll
+                            for (int g = 0; g < MR_G; ++g) a1[o * MR_G + g] = fmaf(v[o], c[g], a1[o * MR_G + g]);
+                    }
+                    if (p.V2) {
+                        mr_load8<CL>(v, p.V2, b, d / K1, D2, h, p.H, w, p.W);
+#pragma unroll
+                        for (int o = 0; o < MR_G; ++o)
+#pragma unroll
+                            for (int g = 0; g < MR_G; ++g) a2[o * MR_G + g] = fmaf(v[o], c[g], a2[o * MR_G + g]);
+                    }
+                }
+            }
+            if constexpr (KT > 0) {
+                if (more) mr_commit<CT, 256>(ring, nb, xn, tid);
+                __syncthreads();
+            }
+        }
+    }
+    float* out = p.ws + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + r) * 128;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+        float x = a1[i], y = a2[i];
+#pragma unroll
+        for (int off = 32; off; off >>= 1) { x += __shfl_xor(x, off); y += __shfl_xor(y, off); }
+        if (lane == 0) { out[i] = x; out[64 + i] = y; }
+    }
+}
+
+// stage 2: block i < 128 (patch i / 64, (o, g) = i % 64) sums the partials of every stage-1 block in a fixed order
+__global__ __launch_bounds__(64) void mr_volume_bwd_w_reduce_kernel(const float* __restrict__ ws, int nblk, float* __restrict__ dP0, float* __restrict__ dP1, int k0, int k1) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    float part[4];
+    for (int r = 0; r < 4; ++r) {
+        float s = 0.f;
+        for (int blk = lane; blk < nblk; blk += 64) s += ws[((size_t)blk * 4 + r) * 128 + i];
+#pragma unroll
+        for (int off = 32; off; off >>= 1) s += __shfl_xor(s, off);
+        part[r] = s;
+    }
+    if (lane == 0) {
+        const int k = (i < 64) ? k0 : k1;
+        float* dP = (i < 64) ? dP0 : dP1;
+        for (int j = 0; j < k; ++j) {
+            float s = 0.f;
+            for (int r = j; r < 4; r += k) s += part[r];
+            dP[(i & 63) * k + j] = s;
+        }
+    }
+}
+
+}  // namespace osa
+
+extern "C" size_t osa_mr_volume_bwd_workspace_bytes(int B, int H, int W, int maxdisp) {
+    if (B <= 0 || H <= 0 || W <= 0 || maxdisp <= 0) return 0;
+    const long long nblk = (long long)B * H * cdiv(W, MR_WT);
+    if (nblk > 0x7fffffffLL) return 0;
+    return (size_t)nblk * cdiv(maxdisp, mr_chunk((int)nblk, maxdisp)) * 4 * 128 * sizeof(float);
+}
+
+extern "C" int osa_mr_volume_bwd_ws_f32(const float* dv0, const float* dv1, const float* dv2, int layout,
+                                        const float* left, const float* right, const float* patch0, const float* patch1,
+                                        float* dleft, float* dright, float* dpatch0, float* dpatch1,
+                                        int B, int C, int H, int W, int num_groups, int out_channels, int maxdisp, int s_range, int m_range, int k0, int k1,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = mr_check("mr_volume_bwd_ws", left && right && patch0 && patch1 && dleft && dright && dpatch0 && dpatch1 && workspace,
+                          B, C, H, W, num_groups, out_channels, maxdisp, s_range, m_range, k0, k1, layout)) return rc;
+    const size_t need = osa_mr_volume_bwd_workspace_bytes(B, H, W, maxdisp);
+    OSA_REQUIRE(workspace_bytes >= need, "mr_volume_bwd_ws: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    MrArgs a{left, right, patch0, patch1, const_cast<float*>(dv0), const_cast<float*>(dv1), const_cast<float*>(dv2), dleft, dright, (float*)workspace,
+             B, C, H, W, maxdisp, s_range, m_range, C / num_groups, cdiv(W, MR_WT), 0};
+    const int nblk = B * H * a.nWt;
+    a.DCH = mr_chunk(nblk, maxdisp);
+    const int nch = cdiv(maxdisp, a.DCH);
+    hipStream_t st = (hipStream_t)stream;
+    mr_dispatch(a.K, k0, k1, layout, [&](auto kt, auto c0, auto c1, auto cl) {
+        constexpr int KT = decltype(kt)::value, A = decltype(c0)::value, E = decltype(c1)::value;
+        constexpr bool CL = decltype(cl)::value;
+        constexpr int CPB = KT ? KT : 1;                    // channels per lane of the data passes (any K: one)
+        hipLaunchKernelGGL((mr_volume_bwd_data_kernel<CPB, A, E, CL, false>), dim3(nblk, C / CPB), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((mr_volume_bwd_data_kernel<CPB, A, E, CL, true>), dim3(nblk, C / CPB), dim3(64), 0, st, a);
+        hipLaunchKernelGGL((mr_volume_bwd_w_kernel<KT, A, E, CL>), dim3(nblk, nch), dim3(256), 0, st, a);
+    });
+    hipLaunchKernelGGL(mr_volume_bwd_w_reduce_kernel, dim3(128), dim3(64), 0, st, (const float*)workspace, nblk * nch, dpatch0, dpatch1, k0, k1);
+    OSA_LAUNCH_CHECK("mr_volume_bwd_ws");
+    return 0;
+}

@@ -70,6 +70,65 @@ at::Tensor corr_volume(const at::Tensor& left, const at::Tensor& right, int64_t 
     return vol;
 }
 
+// IGEV++ multi-range volumes (igevpp_stereo.py:182-186; csrc/mr_volume.h): (V0, V1, V2), each [B, 8, planes, H, W] fp32, contiguous or NDHWC
+struct MrDims { int B, C, H, W, G, Co, k0, k1; };
+static MrDims mr_dims(const at::Tensor& l, const at::Tensor& r, const at::Tensor& p0, const at::Tensor& p1, int64_t D, int64_t S, int64_t M) {
+    TORCH_CHECK(l.dim() == 4 && l.sizes() == r.sizes(), "mr_volume: features must be [B,C,H,W] of equal shape");
+    TORCH_CHECK(p0.dim() == 5 && p1.dim() == 5 && p0.size(3) == 1 && p0.size(4) == 1 && p1.size(3) == 1 && p1.size(4) == 1 && p0.size(0) == p1.size(0) && p0.size(1) == p1.size(1),
+                "mr_volume: patch weights must be [Co, G, k, 1, 1] with equal Co and G");
+    TORCH_CHECK(p0.size(2) > 0 && p1.size(2) > 0 && S > 0 && S <= M && M <= D, "mr_volume: ranges must satisfy 0 < s_range <= m_range <= maxdisp, got ", S, ", ", M, ", ", D);
+    return {(int)l.size(0), (int)l.size(1), (int)l.size(2), (int)l.size(3), (int)p0.size(1), (int)p0.size(0), (int)p0.size(2), (int)p1.size(2)};
+}
+static at::Tensor mr_empty(const at::Tensor& like, int64_t B, int64_t C, int64_t D, int64_t H, int64_t W, bool cl) {
+    const auto o = like.options().dtype(at::kFloat);
+    return cl ? at::empty({B, D, H, W, C}, o).permute({0, 4, 1, 2, 3}) : at::empty({B, C, D, H, W}, o);
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> mr_volume_meta(const at::Tensor& l, const at::Tensor& r, const at::Tensor& p0, const at::Tensor& p1, int64_t D, int64_t S, int64_t M, bool cl) {
+    const MrDims d = mr_dims(l, r, p0, p1, D, S, M);
+    return {mr_empty(l, d.B, d.Co, S, d.H, d.W, cl), mr_empty(l, d.B, d.Co, M / d.k0, d.H, d.W, cl), mr_empty(l, d.B, d.Co, D / d.k1, d.H, d.W, cl)};
+}
+std::tuple<at::Tensor, at::Tensor, at::Tensor> mr_volume(const at::Tensor& left, const at::Tensor& right, const at::Tensor& patch0, const at::Tensor& patch1, int64_t D, int64_t S, int64_t M, bool cl) {
+    gpu_f32(left, "left"); gpu_f32(right, "right"); gpu_f32(patch0, "patch0"); gpu_f32(patch1, "patch1");
+    const MrDims d = mr_dims(left, right, patch0, patch1, D, S, M);
+    const auto l = left.contiguous(), r = right.contiguous(), p0 = patch0.contiguous(), p1 = patch1.contiguous();
+    auto out = mr_volume_meta(l, r, p0, p1, D, S, M, cl);
+    OSA_CALL(osa_mr_volume_f32(fp(l), fp(r), fp(p0), fp(p1), std::get<0>(out).data_ptr<float>(), std::get<1>(out).data_ptr<float>(), std::get<2>(out).data_ptr<float>(),
+                               cl ? OSA_NDHWC : OSA_NCDHW, d.B, d.C, d.H, d.W, d.G, d.Co, (int)D, (int)S, (int)M, d.k0, d.k1, cur_stream()));
+    return out;
+}
+using Tensor4 = std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor>;
+using OptTensor = c10::optional<at::Tensor>;
+Tensor4 mr_volume_bwd_meta(const OptTensor&, const OptTensor&, const OptTensor&, const at::Tensor& l, const at::Tensor& r, const at::Tensor& p0, const at::Tensor& p1, int64_t D, int64_t S, int64_t M, bool) {
+    mr_dims(l, r, p0, p1, D, S, M);
+    const auto o = l.options().dtype(at::kFloat);
+    return {at::empty(l.sizes(), o), at::empty(r.sizes(), o), at::empty(p0.sizes(), o), at::empty(p1.sizes(), o)};
+}
+Tensor4 mr_volume_bwd(const OptTensor& dv0, const OptTensor& dv1, const OptTensor& dv2, const at::Tensor& left, const at::Tensor& right, const at::Tensor& patch0, const at::Tensor& patch1,
+                      int64_t D, int64_t S, int64_t M, bool cl) {
+    gpu_f32(left, "left"); gpu_f32(right, "right"); gpu_f32(patch0, "patch0"); gpu_f32(patch1, "patch1");
+    const MrDims d = mr_dims(left, right, patch0, patch1, D, S, M);
+    const auto l = left.contiguous(), r = right.contiguous(), p0 = patch0.contiguous(), p1 = patch1.contiguous();
+    const int64_t planes[3] = {S, M / d.k0, D / d.k1};
+    at::Tensor dv[3];
+    int i = 0;
+    for (const OptTensor* t : {&dv0, &dv1, &dv2}) {
+        if (t->has_value() && (*t)->defined()) {
+            gpu_f32(**t, "dv");
+            TORCH_CHECK((*t)->sizes() == at::IntArrayRef({d.B, d.Co, planes[i], d.H, d.W}), "mr_volume_bwd: gradient ", i, " has shape ", (*t)->sizes());
+            dv[i] = cl ? (*t)->permute({0, 2, 3, 4, 1}).contiguous() : (*t)->contiguous();
+        }
+        ++i;
+    }
+    auto out = mr_volume_bwd_meta(dv0, dv1, dv2, l, r, p0, p1, D, S, M, cl);
+    const size_t wsb = osa_mr_volume_bwd_workspace_bytes(d.B, d.H, d.W, (int)D);
+    auto ws = at::empty({(int64_t)(wsb / sizeof(float))}, l.options());
+    auto dp = [](const at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
+    OSA_CALL(osa_mr_volume_bwd_ws_f32(dp(dv[0]), dp(dv[1]), dp(dv[2]), cl ? OSA_NDHWC : OSA_NCDHW, fp(l), fp(r), fp(p0), fp(p1),
+                                      std::get<0>(out).data_ptr<float>(), std::get<1>(out).data_ptr<float>(), std::get<2>(out).data_ptr<float>(), std::get<3>(out).data_ptr<float>(),
+                                      d.B, d.C, d.H, d.W, d.G, d.Co, (int)D, (int)S, (int)M, d.k0, d.k1, ws.data_ptr<float>(), wsb, cur_stream()));
+    return out;
+}
+
 // ---- regression heads ----------------------------------------------------------------------------------------------------------
 at::Tensor softargmin(const at::Tensor& prob) {
     gpu_f32(prob, "prob");
@@ -928,6 +987,34 @@ struct GwcVolumeFn : torch::autograd::Function<GwcVolumeFn> {
 };
 at::Tensor gwc_volume_autograd(const at::Tensor& l, const at::Tensor& r, int64_t maxdisp, int64_t groups) { return GwcVolumeFn::apply(l, r, maxdisp, groups); }
 
+// saves the two features and the two weights, nothing of volume size; inputs of other float dtypes are widened, gradients come back in theirs
+struct MrVolumeFn : torch::autograd::Function<MrVolumeFn> {
+    static at::Tensor f32(const at::Tensor& t) { return t.scalar_type() == at::kFloat ? t : t.to(at::kFloat); }     // (no aten::to that returns its input)
+    static variable_list forward(AutogradContext* ctx, const at::Tensor& l, const at::Tensor& r, const at::Tensor& p0, const at::Tensor& p1, int64_t D, int64_t S, int64_t M, bool cl) {
+        at::AutoDispatchBelowADInplaceOrView g;
+        ctx->save_for_backward({l, r, p0, p1});
+        ctx->saved_data["D"] = D; ctx->saved_data["S"] = S; ctx->saved_data["M"] = M; ctx->saved_data["cl"] = cl;
+        ctx->set_materialize_grads(false);
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("osa_native::mr_volume", "")
+            .typed<std::tuple<at::Tensor, at::Tensor, at::Tensor>(const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t, int64_t, bool)>();
+        auto [v0, v1, v2] = op.call(f32(l), f32(r), f32(p0), f32(p1), D, S, M, cl);
+        return {v0, v1, v2};
+    }
+    static variable_list backward(AutogradContext* ctx, variable_list gy) {
+        const auto sv = ctx->get_saved_variables();
+        static auto op = c10::Dispatcher::singleton().findSchemaOrThrow("osa_native::mr_volume_bwd", "")
+            .typed<Tensor4(const OptTensor&, const OptTensor&, const OptTensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, const at::Tensor&, int64_t, int64_t, int64_t, bool)>();
+        auto opt = [](const at::Tensor& t) { return t.defined() ? OptTensor(f32(t)) : OptTensor(); };
+        auto [dl, dr, d0, d1] = op.call(opt(gy[0]), opt(gy[1]), opt(gy[2]), f32(sv[0]), f32(sv[1]), f32(sv[2]), f32(sv[3]),
+                                        ctx->saved_data["D"].toInt(), ctx->saved_data["S"].toInt(), ctx->saved_data["M"].toInt(), ctx->saved_data["cl"].toBool());
+        return {dl.to(sv[0].scalar_type()), dr.to(sv[1].scalar_type()), d0.to(sv[2].scalar_type()), d1.to(sv[3].scalar_type()), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+std::tuple<at::Tensor, at::Tensor, at::Tensor> mr_volume_autograd(const at::Tensor& l, const at::Tensor& r, const at::Tensor& p0, const at::Tensor& p1, int64_t D, int64_t S, int64_t M, bool cl) {
+    const auto v = MrVolumeFn::apply(l, r, p0, p1, D, S, M, cl);
+    return {v[0], v[1], v[2]};
+}
+
 struct ConcatVolumeFn : torch::autograd::Function<ConcatVolumeFn> {
     static at::Tensor forward(AutogradContext* ctx, const at::Tensor& l, const at::Tensor& r, int64_t maxdisp, bool mask_left) {
         at::AutoDispatchBelowADInplaceOrView g;
@@ -1135,6 +1222,8 @@ bool conv_wgrad_multi_meta(at::TensorList xs, at::TensorList dys, at::Tensor dw,
 TORCH_LIBRARY(osa_native, m) {
     m.def("abi_version() -> int", &abi_version);
     m.def("gwc_volume(Tensor left, Tensor right, int maxdisp, int groups) -> Tensor");
+    m.def("mr_volume(Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last=False) -> (Tensor, Tensor, Tensor)");
+    m.def("mr_volume_bwd(Tensor? dv0, Tensor? dv1, Tensor? dv2, Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("concat_volume(Tensor left, Tensor right, int maxdisp, bool mask_left=True) -> Tensor");
     m.def("corr_volume(Tensor left, Tensor right, int maxdisp) -> Tensor");
     m.def("softargmin(Tensor prob) -> Tensor");
@@ -1203,6 +1292,8 @@ TORCH_LIBRARY(osa_native, m) {
 
 TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers under PyTorch's CUDA dispatch key)
     m.impl("gwc_volume", &gwc_volume);
+    m.impl("mr_volume", &mr_volume);
+    m.impl("mr_volume_bwd", &mr_volume_bwd);
     m.impl("concat_volume", &concat_volume);
     m.impl("corr_volume", &corr_volume);
     m.impl("softargmin", &softargmin);
@@ -1264,6 +1355,8 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
 
 TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference without a device: FakeTensor, torch.export, torch.compile
     m.impl("gwc_volume", &gwc_volume_meta);
+    m.impl("mr_volume", &mr_volume_meta);
+    m.impl("mr_volume_bwd", &mr_volume_bwd_meta);
     m.impl("concat_volume", &concat_volume_meta);
     m.impl("corr_volume", &corr_volume_meta);
     m.impl("softargmin", &softargmin_meta);
@@ -1298,6 +1391,7 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
 
 TORCH_LIBRARY_IMPL(osa_native, Autograd, m) {    // differentiable in C++: backward = the engine's *_bwd kernels (no Python autograd.Function involved)
     m.impl("gwc_volume", &gwc_volume_autograd);
+    m.impl("mr_volume", &mr_volume_autograd);
     m.impl("concat_volume", &concat_volume_autograd);
     m.impl("corr_volume", &corr_volume_autograd);
     m.impl("softargmin", &softargmin_autograd);

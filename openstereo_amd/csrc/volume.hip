@@ -988,3 +988,110 @@ extern "C" int osa_corr_volume_f32(const float* left, const float* right, float*
     return osa_build_volume_f32(left, right, C, 1, nullptr, nullptr, 0, vol, OSA_NCDHW, 1, 0,
                                 B, H, W, maxdisp, 1, nullptr, stream);
 }
+
+// ------------------------------------------------------------------ IGEV++ multi-range volumes (mr_volume.h) ----
+// One launch writes V0, V1 and V2.  A workgroup is 64 pixels of one row and a chunk of planes; its four waves share the right window in the
+// LDS ring and take the aligned groups of 4 planes of a step in turn (wave v: (d / 4) % 4 == v; a patch of 2 or 4 planes lies inside one
+// group, so a wave's patch sums are complete), each with the lane's left features in registers.  Per plane the lane forms the 8 group correlations once, stores them while d < S and folds them into
+// the running patch sums, which leave every k0 / k1 planes.  CL: NDHWC stores (32 bytes per voxel), else the reference's NCDHW.
+#include "mr_volume.h"
+namespace osa {
+
+template <int KT, int K0, int K1, bool CL>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void mr_volume_fwd_kernel(const MrArgs p) {
+    constexpr int CT = MR_G * KT;
+    __shared__ float ring[KT ? CT * MR_RING : 1];
+    __shared__ __attribute__((aligned(16))) float Ps0[64 * K0];
+    __shared__ __attribute__((aligned(16))) float Ps1[64 * K1];
+    unsigned bid = blockIdx.x;
+    const int wt = bid % p.nWt; bid /= p.nWt;
+    const int h = bid % p.H, b = bid / p.H;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, w0 = wt * MR_WT, w = w0 + lane;
+    const bool live = w < p.W;
+    const size_t plane = (size_t)p.H * p.W;
+    const float* Lrow = p.L + (size_t)b * p.C * plane + (size_t)h * p.W;
+    const float* Rrow = p.R + (size_t)b * p.C * plane + (size_t)h * p.W;
+    const float Kf = (float)p.K;
+    const int D1 = p.M / K0, D2 = p.D / K1;
+
+    const int d0 = blockIdx.y * p.DCH, dend = min(p.D, d0 + p.DCH);
+    if (d0 > w0 + MR_WT - 1) {                              // no pixel of the tile reaches this chunk: zeros
+        const float z[MR_G] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (live)
+            for (int d = d0; d < dend; ++d) {
+                if (((d >> 2) & 3) != wv) continue;
+                if (d < p.S) mr_store8<CL>(p.V0, z, b, d, p.S, h, p.H, w, p.W);
+                if (d < p.M && d % K0 == K0 - 1) mr_store8<CL>(p.V1, z, b, d / K0, D1, h, p.H, w, p.W);
+                if (d % K1 == K1 - 1) mr_store8<CL>(p.V2, z, b, d / K1, D2, h, p.H, w, p.W);
+            }
+        return;
+    }
+    mr_stage_patch<K0, 256>(Ps0, p.P0, tid);
+    mr_stage_patch<K1, 256>(Ps1, p.P1, tid);
+    float Lr[KT ? CT : 1];
+    if constexpr (KT > 0) {
+#pragma unroll
+        for (int c = 0; c < CT; ++c) Lr[c] = live ? Lrow[(size_t)c * plane + w] : 0.f;
+        mr_stage<CT, 256>(ring, Rrow, plane, p.W, w0 - d0 - MR_DS + 1, MR_WT + MR_DS - 1, tid);
+    }
+    __syncthreads();
+
+    float a1[MR_G], a2[MR_G];
+#pragma unroll
+    for (int o = 0; o < MR_G; ++o) a1[o] = a2[o] = 0.f;
+    // one patch tap: acc[o] += P[o][g][j] * c[g], g ascending
+    auto fold = [&](float (&acc)[MR_G], const float* Ps, const int j, const float (&c)[MR_G]) {
+#pragma unroll
+        for (int g = 0; g < MR_G; ++g) {
+            // (j = d % k at run time: with compile-time taps the compiler hoists all 384 loop-invariant weights into registers)
+            const float4 pa = *reinterpret_cast<const float4*>(Ps + (j * MR_G + g) * MR_G), pb = *reinterpret_cast<const float4*>(Ps + (j * MR_G + g) * MR_G + 4);
+            acc[0] = fmaf(pa.x, c[g], acc[0]); acc[1] = fmaf(pa.y, c[g], acc[1]); acc[2] = fmaf(pa.z, c[g], acc[2]); acc[3] = fmaf(pa.w, c[g], acc[3]);
+            acc[4] = fmaf(pb.x, c[g], acc[4]); acc[5] = fmaf(pb.y, c[g], acc[5]); acc[6] = fmaf(pb.z, c[g], acc[6]); acc[7] = fmaf(pb.w, c[g], acc[7]);
+        }
+    };
+    for (int ds = d0; ds < dend; ds += MR_DS) {
+        [[maybe_unused]] float nb[KT ? CT * MR_DS / 256 : 1];
+        const int xn = w0 + 1 - ds - 2 * MR_DS;                    // first pixel of the next step's new block
+        const bool more = ds + MR_DS < dend;
+        if constexpr (KT > 0) if (more) mr_fetch<CT, 256>(nb, Rrow, plane, p.W, xn, tid);
+#pragma unroll 1
+        for (int d = ds + 4 * wv; d < min(ds + 4 * wv + 4, dend); ++d) {
+            float c[MR_G];
+            mr_gwc<KT>(c, Lr, ring, Lrow, Rrow, plane, p.K, Kf, w, d, live);
+            if (d < p.S && live) mr_store8<CL>(p.V0, c, b, d, p.S, h, p.H, w, p.W);
+            if (d < p.M) {
+                fold(a1, Ps0, d % K0, c);
+                if (d % K0 == K0 - 1) {
+                    if (live) mr_store8<CL>(p.V1, a1, b, d / K0, D1, h, p.H, w, p.W);
+#pragma unroll
+                    for (int o = 0; o < MR_G; ++o) a1[o] = 0.f;
+                }
+            }
+            fold(a2, Ps1, d % K1, c);
+            if (d % K1 == K1 - 1) {
+                if (live) mr_store8<CL>(p.V2, a2, b, d / K1, D2, h, p.H, w, p.W);
+#pragma unroll
+                for (int o = 0; o < MR_G; ++o) a2[o] = 0.f;
+            }
+        }
+        if constexpr (KT > 0) {
+            if (more) mr_commit<CT, 256>(ring, nb, xn, tid);
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace osa
+
+extern "C" int osa_mr_volume_f32(const float* left, const float* right, const float* patch0, const float* patch1, float* v0, float* v1, float* v2, int layout,
+                                 int B, int C, int H, int W, int num_groups, int out_channels, int maxdisp, int s_range, int m_range, int k0, int k1, void* stream) {
+    if (int rc = mr_check("mr_volume", left && right && patch0 && patch1 && v0 && v1 && v2, B, C, H, W, num_groups, out_channels, maxdisp, s_range, m_range, k0, k1, layout)) return rc;
+    MrArgs a{left, right, patch0, patch1, v0, v1, v2, nullptr, nullptr, nullptr, B, C, H, W, maxdisp, s_range, m_range, C / num_groups, cdiv(W, MR_WT), 0};
+    a.DCH = mr_chunk(B * H * a.nWt, maxdisp);
+    mr_dispatch(a.K, k0, k1, layout, [&](auto kt, auto c0, auto c1, auto cl) {
+        hipLaunchKernelGGL((mr_volume_fwd_kernel<decltype(kt)::value, decltype(c0)::value, decltype(c1)::value, decltype(cl)::value>),
+                           dim3(B * H * a.nWt, cdiv(maxdisp, a.DCH)), dim3(256), 0, (hipStream_t)stream, a);
+    });
+    OSA_LAUNCH_CHECK("mr_volume");
+    return 0;
+}

@@ -146,6 +146,20 @@ def build_concat_volume(refimg_fea, targetimg_fea, maxdisp, mask_left=True):
     return v if refimg_fea.dtype == torch.float32 else v.to(refimg_fea.dtype)
 
 
+def build_multirange_volumes(match_left, match_right, patch0_weight, patch1_weight, maxdisp, s_range, m_range, num_groups=8, channels_last=False):
+    """igevpp_stereo.py:182-186 in one launch: build_gwc_volume over maxdisp planes, then (V0, V1, V2) = (its first s_range planes,
+    patch0 = Conv3d(8, 8, (k0,1,1), stride (k0,1,1)) over its first m_range planes, patch1 over all of them).  fp32 [B, 8, planes, H, W],
+    contiguous or NDHWC (channels_last=True: what hourglass.forward_cl takes); differentiable in C++ (features and patch weights), the
+    full-range volume is neither written nor saved.  The outputs feed geometry.MultiRangeGeoEncodingVolume."""
+    for t, name, nd in ((match_left, "match_left", 4), (match_right, "match_right", 4), (patch0_weight, "patch0_weight", 5), (patch1_weight, "patch1_weight", 5)):
+        _chk(t, name, nd)
+    B, Cn, H, W = match_left.shape
+    if patch0_weight.shape[1] != num_groups or patch1_weight.shape[1] != num_groups:
+        raise ValueError(f"patch weights must be [Co, num_groups={num_groups}, k, 1, 1], got {tuple(patch0_weight.shape)} and {tuple(patch1_weight.shape)}")
+    with timing.span("mr_volume", Cn, num_groups, int(maxdisp), int(s_range), int(m_range), H, W):
+        return _ext.load().mr_volume(match_left, match_right, patch0_weight, patch1_weight, int(maxdisp), int(s_range), int(m_range), bool(channels_last))
+
+
 def correlation_volume(left_feature, right_feature, max_disp):
     """cost_volume.py:32-41 -> [B, max_disp, H, W] (mean over all channels)."""
     _chk(left_feature, "left_feature", 4); _chk(right_feature, "right_feature", 4)
@@ -258,13 +272,15 @@ def build_cost_volume_from_cl(gwc_feat, num_groups, cat_feat, B, maxdisp, gwc_ch
 
 
 # --------------------------------------------------------------------------- regression
-def disparity_regression(x, maxdisp, keepdim=True):
-    """disp_regression.py:8-12 (keepdim=True) / gwcnet_disp_processor.py:22-26 (keepdim=False)."""
+def disparity_regression(x, maxdisp, keepdim=True, interval=1):
+    """disp_regression.py:8-12 (keepdim=True) / gwcnet_disp_processor.py:22-26 (keepdim=False); interval: igevpp/submodule.py:147-151,
+    plane i stands for disparity i * interval."""
     assert len(x.shape) == 4                                      # disp_regression.py:9
     _chk(x, "x")
     D = x.shape[1]
-    assert D == maxdisp, f"x has {D} disparity planes, maxdisp={maxdisp}"
+    assert D == maxdisp // interval, f"x has {D} disparity planes, maxdisp={maxdisp}, interval={interval}"
     out = _ext.load().softargmin(_f32c(x))
+    out = out if interval == 1 else out * interval
     out = out if _sum_dtype(x) == torch.float32 else out.to(x.dtype)
     return out.unsqueeze(1) if keepdim else out
 
