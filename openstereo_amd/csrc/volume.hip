@@ -4,13 +4,19 @@
 // writes them straight into the (already concatenated) volume buffer, so the
 // reference's torch.cat (gwcnet_cost_processor.py:65) never happens.
 //
-//  * NDHWC kernel (engine layout): one workgroup per (b, h, 16-pixel w tile, 16-disparity
-//    chunk).  The left tile and the sliding right window are staged channel-permuted in
-//    LDS so that lane g reads its K channels as float4s, conflict free; every wave store
-//    instruction writes one voxel's whole channel vector (G+2Cc floats, 256 B for GwcNet).
+//  * NDHWC (engine layout), three kernels, bit-identical where more than one applies:
+//      - d-walking quad lanes (build_volume_walk_kernel): a workgroup owns a pixel tile of one row and walks along d, the right window
+//        is an LDS ring refilled by a loader wave through LDS-DMA.  NHWC features, 8-wave tiles; fp32 or split (f16x3) output.  The
+//        headline path.
+//      - chunked quad lanes (build_volume_quads_kernel): a workgroup owns (pixel tile, disparity chunk) and stages the whole right window
+//        of the chunk first.  NHWC or NCHW features.
+//      - per channel (build_volume_ndhwc_kernel): lane = output channel; every channel count the quad lanes do not take.
+//    The quad-lane kernels share one definition of the lane's role, of its left features, of a voxel quad and of the running maximum.
 //    HBM-write bound: 4 B written per 8 FMAs.
 //  * NCDHW kernel (reference layout, drop-in functions): lanes run along w, so loads and
 //    stores are coalesced rows; operands come from L1/L2.
+//  * dormant pair volumes, cat_fms, and the IGEV++ multi-range volumes (mr_volume.h).
+// Host side: build_volume_impl validates and chooses; launch_walk / launch_quads / launch_perchannel / launch_ncdhw size and launch.
 #include "osa_common.h"
 #include <type_traits>
 
@@ -32,6 +38,28 @@ struct VolArgs {
 
 constexpr int VOL_WT = 16;   // output pixels per tile
 constexpr int VOL_DCH = 16;  // disparities per chunk
+
+// Channels [c, c + 4) of pixel (b, h, w) of a feature map with Ct channels.  stride > 0: NHWC with `stride` floats per pixel, one float4;
+// stride == 0: NCHW, four plane-strided scalars.  NHWC = true (the walking kernel): the features are NHWC with 16-byte aligned quads by
+// eligibility, no run-time test.
+typedef float vol_f32x4_t __attribute__((ext_vector_type(4), aligned(4)));   // (concat features promise 4-byte alignment only)
+template <bool NHWC = false>
+__device__ __forceinline__ float4 load_quad(const float* f, const int stride, const int Ct, const VolArgs& p, const int b, const int h, const int w, const int c) {
+    if constexpr (NHWC) return *reinterpret_cast<const float4*>(f + (((size_t)b * p.H + h) * p.W + w) * stride + c);
+    if (stride) {
+        // (a native vector: as four scalars beside the NCHW form's four, the compiler merges the two forms into stride-selected scalar loads)
+        const vol_f32x4_t t = *reinterpret_cast<const vol_f32x4_t*>(f + (((size_t)b * p.H + h) * p.W + w) * stride + c);
+        return make_float4(t.x, t.y, t.z, t.w);
+    }
+    const size_t plane = (size_t)p.H * p.W;
+    const float* src = f + ((size_t)b * Ct + c) * plane + (size_t)h * p.W + w;
+    return make_float4(src[0], src[plane], src[2 * plane], src[3 * plane]);
+}
+
+// running maximum of |value| over a stored quad (by value: with `am` by reference the chunked kernel's d loop loses its remainder form)
+__device__ __forceinline__ float amax4(const float am, const float4& o) {
+    return fmaxf(am, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
+}
 
 template <int QG>  // K/4 : float4s per group
 __global__ __launch_bounds__(256) void build_volume_ndhwc_kernel(const VolArgs p) {
@@ -70,15 +98,9 @@ __global__ __launch_bounds__(256) void build_volume_ndhwc_kernel(const VolArgs p
             if (qi < nq_g) {
                 const int q = qi / p.G, g = qi - q * p.G;
                 lpos = qi * 4;
-                if (wok) {
-                    if (p.gstride) {
-                        v = *reinterpret_cast<const float4*>(fg + (((size_t)b * p.H + h) * p.W + w) * p.gstride + g * p.K + q * 4);
-                    } else {
-                        const float* src = fg + ((size_t)b * p.C + (size_t)g * p.K + q * 4) * plane + (size_t)h * p.W + w;
-                        v.x = src[0]; v.y = src[plane]; v.z = src[2 * plane]; v.w = src[3 * plane];
-                    }
-                }
+                if (wok) v = load_quad(fg, p.gstride, p.C, p, b, h, w, g * p.K + q * 4);
             } else {
+                // (the last concat quad may be ragged, Cc % 4 != 0: scalars with a count, not load_quad)
                 const int qc = qi - nq_g;
                 lpos = p.catbase + qc * 4;
                 if (wok) {
@@ -102,8 +124,6 @@ __global__ __launch_bounds__(256) void build_volume_ndhwc_kernel(const VolArgs p
     // ---- compute: lane = output channel, wave = pixel
     const int lane = tid & 63, wave = tid >> 6;
     const int nch = p.G + 2 * p.Cc;
-    const float invK = 1.0f / (float)p.K;
-    (void)invK;
     float am = 0.f;
     const unsigned am_seen = p.meta ? amax_peek(p.meta) : 0u;
     for (int c = lane; c < nch; c += 64) {
@@ -166,7 +186,6 @@ __global__ __launch_bounds__(256) void build_volume_ndhwc_kernel(const VolArgs p
 struct VolQArgs {
     VolArgs v;
     int NQ, lgNQ, DCH, RSq;
-    int dbg;               // timing experiments only (OSA_VOL_DBG): 1 = no stores, 2 = no dot products, 4 = no window staging
     // d-walking form, split output (f16x3 chains): the volume is written as a split tensor -- every 16-channel chunk [16 x fp16 hi | 16 x fp16 lo],
     // the bytes of fp32 NDHWC -- scaled by a power of two derived from the FEATURES' range blocks (a bound, known before the first voxel
     // exists: |gwc| <= max|f|^2, |concat| <= max|f_cat|), so that the first aggregation layer stages it by LDS-DMA like every other layer of
@@ -175,15 +194,80 @@ struct VolQArgs {
     const float* gmeta; const float* cmeta;     // range blocks of the gwc / concat feature tensors (left and right images in one tensor)
 };
 
-// PX2: a lane owns TWO pixels, w and w + vpw.  out(w, d) and out(w + vpw, d + vpw) read the same right vector R[w - d], so walking the
-// window once serves both: the kernel is bound by LDS reads (8 float4 per lane and (w, d): 983 KB per workgroup for 196 KB of output),
-// and this cuts them by DCH / (DCH + vpw) * 2 = 1.7x at the price of a second set of left registers.  Stores stay 1 KB contiguous.
-template <int QG, int NWV, bool PX2 = false>     // NWV waves per workgroup (4 or 8): a wider pixel tile amortises the right window
+// A lane of the quad-lane kernels: quad cq of the voxel of pixel (wave's first pixel + wsub).
+struct QuadLane {
+    int cq, wsub, G4;
+    int role;              // 0 gwc quad (groups 4 cq .. 4 cq + 3) / 1 left concat quad / 2 right concat quad
+    int rq;                // role 2: slot of the quad in a window row
+};
+template <int QG>
+__device__ __forceinline__ QuadLane quad_lane(const VolQArgs& q, const int lane) {
+    QuadLane l;
+    l.G4 = q.v.G >> 2;
+    const int nq_g = QG * q.v.G, nq_c = q.v.Cc >> 2;
+    l.cq = lane & (q.NQ - 1); l.wsub = lane >> q.lgNQ;
+    l.role = (l.cq < l.G4) ? 0 : ((l.cq < l.G4 + nq_c) ? 1 : 2);
+    l.rq = nq_g + (l.cq - l.G4 - nq_c);
+    return l;
+}
+
+// The lane's left features of pixel w (live: w is inside the map): 4 groups x QG float4s (role 0) or one concat quad (role 1), zeros otherwise.
+template <int QG, bool NHWC>
+__device__ __forceinline__ void load_left(const VolArgs& p, const QuadLane& l, const int b, const int h, const int w, const bool live,
+                                          float4 (&Lr)[4 * QG], float4& lcat) {
+    lcat = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int i = 0; i < 4 * QG; ++i) Lr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live && l.role == 0) {
+#pragma unroll
+        for (int gi = 0; gi < 4; ++gi)
+#pragma unroll
+            for (int kq = 0; kq < QG; ++kq) Lr[gi * QG + kq] = load_quad<NHWC>(p.lg, p.gstride, p.C, p, b, h, w, (l.cq * 4 + gi) * p.K + kq * 4);
+    } else if (live && l.role == 1) {
+        lcat = load_quad<NHWC>(p.lc, p.cstride, p.Cc, p, b, h, w, (l.cq - l.G4) * 4);
+    }
+}
+
+// One output quad from the window row rrow (the right pixel w - d): 4 group means (k-ordered fmaf chains: gi outer, kq inner, x y z w),
+// the left concat quad, or the right one.  valid: w >= d.
+template <int QG>
+__device__ __forceinline__ float4 voxel_quad(const QuadLane& l, const bool valid, const float4 (&Lr)[4 * QG], const float4& lcat,
+                                             const float4* win, const size_t row, const int mask_left, const int K) {
+    const float4* rrow = win + row;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (l.role == 0) {
+        const float Kf = (float)K;
+        // mean over K channels: for K a power of two the multiply by 1/K is exact (== the division)
+        const bool kpow2 = (K & (K - 1)) == 0;
+        const float Kinv = 1.0f / Kf;
+        float sv[4];
+#pragma unroll
+        for (int gi = 0; gi < 4; ++gi) {
+            float s = 0.f;
+#pragma unroll
+            for (int kq = 0; kq < QG; ++kq) {
+                const float4 r = rrow[(gi * QG + kq) * l.G4 + l.cq];
+                const float4 f = Lr[gi * QG + kq];
+                s = fmaf(f.x, r.x, s); s = fmaf(f.y, r.y, s);
+                s = fmaf(f.z, r.z, s); s = fmaf(f.w, r.w, s);
+            }
+            sv[gi] = valid ? (kpow2 ? s * Kinv : s / Kf) : 0.f;
+        }
+        o = make_float4(sv[0], sv[1], sv[2], sv[3]);
+    } else if (l.role == 1) {
+        if (valid || !mask_left) o = lcat;
+    } else {
+        if (valid) o = rrow[l.rq];
+    }
+    return o;
+}
+
+template <int QG, int NWV>     // NWV waves per workgroup (4 or 8): a wider pixel tile amortises the right window
 __global__ __launch_bounds__(NWV * 64) void build_volume_quads_kernel(const VolQArgs q) {
     extern __shared__ __attribute__((aligned(16))) float4 smq[];
     const VolArgs& p = q.v;
     constexpr int NTHR = NWV * 64;
-    const int vpw = 64 >> q.lgNQ, WT = NWV * vpw * (PX2 ? 2 : 1);
+    const int vpw = 64 >> q.lgNQ, WT = NWV * vpw;
     const int NPXR = WT + q.DCH - 1;
 
     unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
@@ -195,54 +279,22 @@ __global__ __launch_bounds__(NWV * 64) void build_volume_quads_kernel(const VolQ
     const int wr0 = w0 - (d0 + q.DCH - 1);            // first right pixel of the window
 
     const int tid = threadIdx.x;
-    const size_t plane = (size_t)p.H * p.W;
-    const int G4 = p.G >> 2;
-    const int nq_g = QG * p.G, nq_c = p.Cc >> 2, nq = nq_g + nq_c;
-    const size_t rowpix = ((size_t)b * p.H + h) * p.W;
+    const int nq_g = QG * p.G, nq = nq_g + (p.Cc >> 2);
 
     // ---- this lane's voxel column and role; its left features are requested first so that their
     // latency overlaps the staging of the right window
     const int lane = tid & 63, wave = tid >> 6;
-    const int cq = lane & (q.NQ - 1), wsub = lane >> q.lgNQ;
-    const int w = w0 + wave * vpw * (PX2 ? 2 : 1) + wsub;          // PX2: the lane's first pixel; the second is w + vpw
+    const QuadLane l = quad_lane<QG>(q, lane);
+    const int w = w0 + wave * vpw + l.wsub;
     const bool wlive = w < p.W;
-    const int role = (cq < G4) ? 0 : ((cq < G4 + nq_c) ? 1 : 2);   // gwc quad / left concat quad / right concat quad
-    float4 Lr[4 * QG], Lr2[PX2 ? 4 * QG : 1];
-    float4 lcat = make_float4(0.f, 0.f, 0.f, 0.f), lcat2 = lcat;
-    auto load_left = [&](int wp, float4* L, float4& lc) {
-#pragma unroll
-        for (int i = 0; i < 4 * QG; ++i) L[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (wp < p.W && role == 0) {
-#pragma unroll
-            for (int gi = 0; gi < 4; ++gi)
-#pragma unroll
-                for (int kq = 0; kq < QG; ++kq) {
-                    const int g = cq * 4 + gi;
-                    if (p.gstride) L[gi * QG + kq] = *reinterpret_cast<const float4*>(p.lg + (rowpix + wp) * p.gstride + g * p.K + kq * 4);
-                    else {
-                        const float* src = p.lg + ((size_t)b * p.C + (size_t)g * p.K + kq * 4) * plane + (size_t)h * p.W + wp;
-                        L[gi * QG + kq] = make_float4(src[0], src[plane], src[2 * plane], src[3 * plane]);
-                    }
-                }
-        } else if (wp < p.W && role == 1) {
-            const int qc = cq - G4;
-            if (p.cstride) {
-                const float* src = p.lc + (rowpix + wp) * p.cstride + qc * 4;
-                lc = make_float4(src[0], src[1], src[2], src[3]);
-            } else {
-                const float* src = p.lc + ((size_t)b * p.Cc + qc * 4) * plane + (size_t)h * p.W + wp;
-                lc = make_float4(src[0], src[plane], src[2 * plane], src[3 * plane]);
-            }
-        }
-    };
-    load_left(w, Lr, lcat);
-    if constexpr (PX2) load_left(w + vpw, Lr2, lcat2);
+    float4 Lr[4 * QG], lcat;
+    load_left<QG, false>(p, l, b, h, w, wlive, Lr, lcat);
     // ---- right window -> LDS.  Source quad (g, kq) goes to slot (g&3)*QG*G4 + kq*G4 + (g>>2).
     // Item = (pixel, quad); the fast index follows the feature layout (NHWC: quads of a pixel, NCHW:
     // pixels of a quad).  A thread walks its items with a carry instead of dividing, and keeps 4
     // loads in flight before the first LDS store.
     {
-        const int items = (q.dbg & 4) ? 0 : nq * NPXR;
+        const int items = nq * NPXR;
         const bool chan_fast = (p.gstride != 0);
         const int inner = chan_fast ? nq : NPXR;      // extent of the fast index
         const int step_hi = NTHR / inner, step_lo = NTHR - step_hi * inner;
@@ -256,31 +308,16 @@ __global__ __launch_bounds__(NWV * 64) void build_volume_quads_kernel(const VolQ
                 v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
                 dst[u] = -1;
                 if (it0 + u * NTHR < items) {
-                    const int w = wr0 + px;
-                    const bool wok = (w >= 0) && (w < p.W);
+                    const int wr = wr0 + px;
+                    const bool wok = (wr >= 0) && (wr < p.W);
                     int pos;
                     if (qi < nq_g) {
                         const int g = qi / QG, kq = qi - g * QG;
-                        pos = ((g & 3) * QG + kq) * G4 + (g >> 2);
-                        if (wok) {
-                            if (p.gstride) v[u] = *reinterpret_cast<const float4*>(p.rg + (rowpix + w) * p.gstride + g * p.K + kq * 4);
-                            else {
-                                const float* src = p.rg + ((size_t)b * p.C + (size_t)g * p.K + kq * 4) * plane + (size_t)h * p.W + w;
-                                v[u] = make_float4(src[0], src[plane], src[2 * plane], src[3 * plane]);
-                            }
-                        }
+                        pos = ((g & 3) * QG + kq) * l.G4 + (g >> 2);
+                        if (wok) v[u] = load_quad(p.rg, p.gstride, p.C, p, b, h, wr, g * p.K + kq * 4);
                     } else {
-                        const int qc = qi - nq_g;
                         pos = qi;
-                        if (wok) {
-                            if (p.cstride) {
-                                const float* src = p.rc + (rowpix + w) * p.cstride + qc * 4;
-                                v[u] = make_float4(src[0], src[1], src[2], src[3]);
-                            } else {
-                                const float* src = p.rc + ((size_t)b * p.Cc + qc * 4) * plane + (size_t)h * p.W + w;
-                                v[u] = make_float4(src[0], src[plane], src[2 * plane], src[3 * plane]);
-                            }
-                        }
+                        if (wok) v[u] = load_quad(p.rc, p.cstride, p.Cc, p, b, h, wr, (qi - nq_g) * 4);
                     }
                     dst[u] = px * q.RSq + pos;
                 }
@@ -295,87 +332,18 @@ __global__ __launch_bounds__(NWV * 64) void build_volume_quads_kernel(const VolQ
 
     __syncthreads();
 
-    const float Kf = (float)p.K;
-    // mean over K channels: for K a power of two the multiply by 1/K is exact (== the division)
-    const bool kpow2 = (p.K & (p.K - 1)) == 0;
-    const float Kinv = 1.0f / Kf;
-    const int rq = nq_g + (cq - G4 - nq_c);           // right-concat slot of this lane (role 2)
-    float* vout = p.vol + p.coff + cq * 4;
+    float* vout = p.vol + p.coff + l.cq * 4;
     float am = 0.f;
     const unsigned am_seen = p.meta ? amax_peek(p.meta) : 0u;
-    // one output quad of pixel wp at disparity d from the window row rrow (R[wp - d])
-    auto emit = [&](int wp, int d, const float4* rrow, const float4* L, const float4& lc) {
-        const bool valid = (wp >= d);
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (role == 0 && !(q.dbg & 2)) {
-            float sv[4];
-#pragma unroll
-            for (int gi = 0; gi < 4; ++gi) {
-                float s_ = 0.f;
-#pragma unroll
-                for (int kq = 0; kq < QG; ++kq) {
-                    const float4 r = rrow[(gi * QG + kq) * G4 + cq];
-                    const float4 l = L[gi * QG + kq];
-                    s_ = fmaf(l.x, r.x, s_); s_ = fmaf(l.y, r.y, s_);
-                    s_ = fmaf(l.z, r.z, s_); s_ = fmaf(l.w, r.w, s_);
-                }
-                sv[gi] = valid ? (kpow2 ? s_ * Kinv : s_ / Kf) : 0.f;
-            }
-            o = make_float4(sv[0], sv[1], sv[2], sv[3]);
-        } else if (role == 1) {
-            if (valid || !p.mask_left) o = lc;
-        } else {
-            if (valid) o = rrow[rq];
-        }
-        if (wp < p.W && (!(q.dbg & 1) || o.x == 12345.678f)) {
-            const size_t vox = (((size_t)b * p.D + d) * p.H + h) * p.W + wp;
-            store16(vout + vox * p.VC, o);
-            am = fmaxf(am, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
-        }
-    };
-    if constexpr (PX2) {
-        // t walks the window rows both pixels need: row(t) = R[(w + vpw) - (d0 + t)] serves pixel w + vpw at dd = t and pixel w at dd = t - vpw
-        const int c2 = wave * vpw * 2 + wsub + vpw;             // window column of the second pixel
-#pragma unroll 4
-        for (int t = 0; t < q.DCH + vpw; ++t) {
-            const float4* rrow = smq + (size_t)(c2 + q.DCH - 1 - t) * q.RSq;
-            if (t < q.DCH && d0 + t < p.D) emit(w + vpw, d0 + t, rrow, Lr2, lcat2);
-            if (t >= vpw && d0 + t - vpw < p.D) emit(w, d0 + t - vpw, rrow, Lr, lcat);
-        }
-        if (p.meta) publish_amax(p.meta, am, am_seen, reinterpret_cast<float*>(smq));
-        return;
-    }
 #pragma unroll 4
     for (int dd = 0; dd < q.DCH; ++dd) {
         const int d = d0 + dd;
         if (d >= p.D) break;
-        const bool valid = (w >= d);
-        const float4* rrow = smq + (size_t)(wave * vpw + wsub + q.DCH - 1 - dd) * q.RSq;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (role == 0 && !(q.dbg & 2)) {
-            float sv[4];
-#pragma unroll
-            for (int gi = 0; gi < 4; ++gi) {
-                float s = 0.f;
-#pragma unroll
-                for (int kq = 0; kq < QG; ++kq) {
-                    const float4 r = rrow[(gi * QG + kq) * G4 + cq];
-                    const float4 l = Lr[gi * QG + kq];
-                    s = fmaf(l.x, r.x, s); s = fmaf(l.y, r.y, s);
-                    s = fmaf(l.z, r.z, s); s = fmaf(l.w, r.w, s);
-                }
-                sv[gi] = valid ? (kpow2 ? s * Kinv : s / Kf) : 0.f;
-            }
-            o = make_float4(sv[0], sv[1], sv[2], sv[3]);
-        } else if (role == 1) {
-            if (valid || !p.mask_left) o = lcat;
-        } else {
-            if (valid) o = rrow[rq];
-        }
-        if (wlive && (!(q.dbg & 1) || o.x == 12345.678f)) {
+        const float4 o = voxel_quad<QG>(l, w >= d, Lr, lcat, smq, (size_t)(wave * vpw + l.wsub + q.DCH - 1 - dd) * q.RSq, p.mask_left, p.K);
+        if (wlive) {
             const size_t vox = (((size_t)b * p.D + d) * p.H + h) * p.W + w;
             store16(vout + vox * p.VC, o);
-            am = fmaxf(am, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
+            am = amax4(am, o);
         }
     }
     if (p.meta) publish_amax(p.meta, am, am_seen, reinterpret_cast<float*>(smq));
@@ -395,7 +363,7 @@ __global__ __launch_bounds__(NWV * 64) void build_volume_quads_kernel(const VolQ
 //     overwrites was last read at least one step -- one barrier -- earlier (derivation next to the kernel).
 //   * staged bytes per output byte fall from (WT + DCH - 1) / (WT DCH) to (WT + D - 1) / (WT D) pixels per voxel row (0.36 -> 0.26 of the
 //     window per output for GwcNet), and there is no second pass over the left features.
-// Same lanes, same k-ordered fmaf chains, same stores as the kernel above: bit-identical output (tests/test_gpu_parity.py).
+// Same lanes, same voxel_quad, same stores as the kernel above: bit-identical output (tests/test_gpu_parity.py).
 // NHWC features with 16-byte aligned quads only (the engine's backbone output); everything else keeps the kernel above.
 __device__ const float4 g_vol_zeros[64] = {};        // source of the ring slots outside the image / beyond a pixel's quads
 
@@ -423,77 +391,49 @@ __global__ __launch_bounds__((NWV + 1) * 64) void build_volume_walk_kernel(const
     const int nsteps = (p.D + DS - 1) / DS;
     float* const red = reinterpret_cast<float*>(smq + (size_t)NRING * q.RSq);      // publish_amax scratch (NWV + 1 floats) above the ring
 
-    // ---- LDS-DMA of ring block `blk` <- right pixels [x0, x0 + DS).  Slot j of the block = (pixel j / RSq, position j % RSq); the
-    // position -> source quad map is the inverse of the staging permutation of the kernel above.  Issued by `nw` waves, wave `iw` of them.
+    // ---- LDS-DMA instruction i of ring block `blk` <- right pixels [x0, x0 + DS): 64 slots.  Slot j of the block = (pixel j / RSq, position
+    // j % RSq); the position -> source quad map is the inverse of the staging permutation of the kernel above.
     const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smq;
-    auto dma_block = [&](const int blk, const int x0, const int iw, const int nw) {
-        for (int i = iw; i < NI; i += nw) {
-            const int j = i * 64 + lane;
-            const int px = j / q.RSq, pos = j - px * q.RSq;
-            const int x = x0 + px;
-            const char* src = reinterpret_cast<const char*>(g_vol_zeros) + lane * 16;
-            if (j < BLKQ && pos < nq && x >= 0 && x < p.W) {
-                if (pos < nq_g) {
-                    const int a = pos / G4, ghi = pos - a * G4;
-                    const int g = ghi * 4 + a / QG, kq = a - (a / QG) * QG;
-                    src = reinterpret_cast<const char*>(p.rg + (rowpix + x) * p.gstride + g * p.K + kq * 4);
-                } else src = reinterpret_cast<const char*>(p.rc + (rowpix + x) * p.cstride + (pos - nq_g) * 4);
-            }
-            const unsigned m0v = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)((blk * BLKQ + i * 64) * 16));
-            if (j < BLKQ) {
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src), "s"(m0v) : "memory");
-            }
+    auto dma_slice = [&](const int blk, const int x0, const int i) {
+        const int j = i * 64 + lane;
+        const int px = j / q.RSq, pos = j - px * q.RSq;
+        const int x = x0 + px;
+        const char* src = reinterpret_cast<const char*>(g_vol_zeros) + lane * 16;
+        if (j < BLKQ && pos < nq && x >= 0 && x < p.W) {
+            if (pos < nq_g) {
+                const int a = pos / G4, ghi = pos - a * G4;
+                const int g = ghi * 4 + a / QG, kq = a - (a / QG) * QG;
+                src = reinterpret_cast<const char*>(p.rg + (rowpix + x) * p.gstride + g * p.K + kq * 4);
+            } else src = reinterpret_cast<const char*>(p.rc + (rowpix + x) * p.cstride + (pos - nq_g) * 4);
+        }
+        const unsigned m0v = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)((blk * BLKQ + i * 64) * 16));
+        if (j < BLKQ) {
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(src), "s"(m0v) : "memory");
         }
     };
     // block index of the pixels [w0 + 1 + k DS, w0 + (k + 1) DS], k may be negative
     auto blk_of = [&](int k) { k %= NB; return k < 0 ? k + NB : k; };
+    // a whole ring block by one wave
+    auto dma_block = [&](const int blk, const int x0) {
+        for (int i = 0; i < NI; ++i) dma_slice(blk, x0, i);
+    };
 
     // ---- prologue: every wave requests its left features (compute waves), then all NWV + 1 waves share the initial window:
     // blocks 0 .. WT / DS - 1 (pixels w0 + 1 .. w0 + WT) and block -1 (step 0's left pixels w0 + 1 - DS .. w0)
-    const int cq = lane & (q.NQ - 1), wsub = lane >> q.lgNQ;
+    const QuadLane l = quad_lane<QG>(q, lane);
     const bool compute = wave < NWV;
-    const int w = w0 + wave * vpw + wsub;
+    const int w = w0 + wave * vpw + l.wsub;
     const bool wlive = compute && w < p.W;
-    const int role = (cq < G4) ? 0 : ((cq < G4 + nq_c) ? 1 : 2);
-    float4 Lr[4 * QG];
-    float4 lcat = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int i = 0; i < 4 * QG; ++i) Lr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (wlive && role == 0) {
-#pragma unroll
-        for (int gi = 0; gi < 4; ++gi)
-#pragma unroll
-            for (int kq = 0; kq < QG; ++kq)
-                Lr[gi * QG + kq] = *reinterpret_cast<const float4*>(p.lg + (rowpix + w) * p.gstride + (cq * 4 + gi) * p.K + kq * 4);
-    } else if (wlive && role == 1) {
-        const float* src = p.lc + (rowpix + w) * p.cstride + (cq - G4) * 4;
-        lcat = make_float4(src[0], src[1], src[2], src[3]);
-    }
+    float4 Lr[4 * QG], lcat;
+    load_left<QG, true>(p, l, b, h, w, wlive, Lr, lcat);
     {
         const int nbi = WT / DS + 1;                      // blocks of the initial window
         for (int t = wave; t < nbi * NI; t += NWV + 1) {  // (block, instruction) pairs round-robin over the waves
             const int kb = t / NI, i = t - kb * NI;
             const int k = (kb < WT / DS) ? kb : -1;
-            // one instruction: reuse dma_block's body through a 1-wave slice
-            const int j = i * 64 + lane;
-            const int px = j / q.RSq, pos = j - px * q.RSq;
-            const int x = w0 + 1 + k * DS + px;
-            const char* src = reinterpret_cast<const char*>(g_vol_zeros) + lane * 16;
-            if (j < BLKQ && pos < nq && x >= 0 && x < p.W) {
-                if (pos < nq_g) {
-                    const int a = pos / G4, ghi = pos - a * G4;
-                    const int g = ghi * 4 + a / QG, kq = a - (a / QG) * QG;
-                    src = reinterpret_cast<const char*>(p.rg + (rowpix + x) * p.gstride + g * p.K + kq * 4);
-                } else src = reinterpret_cast<const char*>(p.rc + (rowpix + x) * p.cstride + (pos - nq_g) * 4);
-            }
-            const unsigned m0v = __builtin_amdgcn_readfirstlane(smem_lds + (unsigned)((blk_of(k) * BLKQ + i * 64) * 16));
-            if (j < BLKQ) {
-                unsigned keep;
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src), "s"(m0v) : "memory");
-            }
+            dma_slice(blk_of(k), w0 + 1 + k * DS, i);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (also the left features: requested above, needed below)
@@ -504,17 +444,13 @@ __global__ __launch_bounds__((NWV + 1) * 64) void build_volume_walk_kernel(const
     if (!compute) {
         // ================= loader wave: block of step s + 1 while the compute waves run step s =================
         for (int s = 0; s < nsteps; ++s) {
-            if (s + 1 < nsteps) dma_block(blk_of(-(s + 2)), w0 + 1 - (s + 2) * DS, 0, 1);
+            if (s + 1 < nsteps) dma_block(blk_of(-(s + 2)), w0 + 1 - (s + 2) * DS);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
     } else {
         // ================= compute waves =================
-        const float Kf = (float)p.K;
-        const bool kpow2 = (p.K & (p.K - 1)) == 0;
-        const float Kinv = 1.0f / Kf;
-        const int rq = nq_g + (cq - G4 - nq_c);
-        float* vout = p.vol + p.coff + cq * 4;
+        float* vout = p.vol + p.coff + l.cq * 4;
         // split output: scale from the features' ranges (wave-uniform); lanes (cq even, cq + 1) of a voxel pair up -- the even lane stores the
         // 16 bytes of hi halves of both quads, the odd lane the 16 bytes of lo halves (one 16-byte store per lane, as for fp32)
         [[maybe_unused]] float s_out = 1.f;
@@ -523,56 +459,32 @@ __global__ __launch_bounds__((NWV + 1) * 64) void build_volume_walk_kernel(const
             s_out = pow2_scale(fmaxf(ag * ag, ac) * 1.0625f);
             if (p.meta && blockIdx.x == 0 && tid == 0) p.meta[1] = s_out;
         }
-        const int cch = p.coff + cq * 4;                       // first channel of this lane's quad
-        [[maybe_unused]] float* const vsplit = p.vol + (cch >> 4) * 16 + ((cq & 1) ? 8 : 0) + (((cch & 15) >> 3) * 4);
+        const int cch = p.coff + l.cq * 4;                     // first channel of this lane's quad
+        [[maybe_unused]] float* const vsplit = p.vol + (cch >> 4) * 16 + ((l.cq & 1) ? 8 : 0) + (((cch & 15) >> 3) * 4);
         int ri = w - (w0 + 1);                                // ring slot of pixel w - d, d = 0 (in [-1, WT - 2])
         if (ri < 0) ri += NRING;
         // (measured and NOT kept: walking the ring offset and the output pointer incrementally instead of recomputing them per disparity --
         // fewer VALU instructions, but a loop-carried chain through the unrolled body: 0.97 -> 1.17 ms at 8 pairs, profiles/round4/volume_walk_incremental_addresses.txt)
         // one disparity of this lane's voxel column
         auto emit = [&](const int d) {
-            {
-                const bool valid = (w >= d);
-                const float4* rrow = smq + (size_t)ri * q.RSq;
-                ri = (ri == 0) ? NRING - 1 : ri - 1;
-                float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (role == 0) {
-                    float sv[4];
-#pragma unroll
-                    for (int gi = 0; gi < 4; ++gi) {
-                        float sacc = 0.f;
-#pragma unroll
-                        for (int kq = 0; kq < QG; ++kq) {
-                            const float4 r = rrow[(gi * QG + kq) * G4 + cq];
-                            const float4 l = Lr[gi * QG + kq];
-                            sacc = fmaf(l.x, r.x, sacc); sacc = fmaf(l.y, r.y, sacc);
-                            sacc = fmaf(l.z, r.z, sacc); sacc = fmaf(l.w, r.w, sacc);
-                        }
-                        sv[gi] = valid ? (kpow2 ? sacc * Kinv : sacc / Kf) : 0.f;
-                    }
-                    o = make_float4(sv[0], sv[1], sv[2], sv[3]);
-                } else if (role == 1) {
-                    if (valid || !p.mask_left) o = lcat;
-                } else {
-                    if (valid) o = rrow[rq];
-                }
-                if constexpr (SPLIT) {
-                    uint2 h2, l2;
-                    split_f16(mul4(o, s_out), h2, l2);
-                    const bool odd = (cq & 1) != 0;
-                    const uint2 send = odd ? h2 : l2;            // what the partner lane stores
-                    const uint2 recv = make_uint2((unsigned)__builtin_amdgcn_mov_dpp((int)send.x, 0xB1, 0xf, 0xf, true),     // quad_perm [1, 0, 3, 2]
-                                                  (unsigned)__builtin_amdgcn_mov_dpp((int)send.y, 0xB1, 0xf, 0xf, true));
-                    if (wlive) {
-                        const size_t vox = (((size_t)b * p.D + d) * p.H + h) * p.W + w;
-                        store16(vsplit + vox * p.VC, odd ? make_uint4(recv.x, recv.y, l2.x, l2.y) : make_uint4(h2.x, h2.y, recv.x, recv.y));
-                        am = fmaxf(am, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
-                    }
-                } else if (wlive) {
+            const float4 o = voxel_quad<QG>(l, w >= d, Lr, lcat, smq, (size_t)ri * q.RSq, p.mask_left, p.K);
+            ri = (ri == 0) ? NRING - 1 : ri - 1;
+            if constexpr (SPLIT) {
+                uint2 h2, l2;
+                split_f16(mul4(o, s_out), h2, l2);
+                const bool odd = (l.cq & 1) != 0;
+                const uint2 send = odd ? h2 : l2;            // what the partner lane stores
+                const uint2 recv = make_uint2((unsigned)__builtin_amdgcn_mov_dpp((int)send.x, 0xB1, 0xf, 0xf, true),     // quad_perm [1, 0, 3, 2]
+                                              (unsigned)__builtin_amdgcn_mov_dpp((int)send.y, 0xB1, 0xf, 0xf, true));
+                if (wlive) {
                     const size_t vox = (((size_t)b * p.D + d) * p.H + h) * p.W + w;
-                    store16(vout + vox * p.VC, o);
-                    am = fmaxf(am, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
+                    store16(vsplit + vox * p.VC, odd ? make_uint4(recv.x, recv.y, l2.x, l2.y) : make_uint4(h2.x, h2.y, recv.x, recv.y));
+                    am = amax4(am, o);
                 }
+            } else if (wlive) {
+                const size_t vox = (((size_t)b * p.D + d) * p.H + h) * p.W + w;
+                store16(vout + vox * p.VC, o);
+                am = amax4(am, o);
             }
         };
         for (int s = 0; s < nsteps; ++s) {
@@ -604,15 +516,7 @@ __global__ __launch_bounds__((NWV + 1) * 64) void build_volume_walk_kernel(const
 
 // ------------------------------------------------------------------ NCDHW ----
 // One thread per output element, w fastest. grid.y = channel, grid.z = b*D+d.
-struct VolNArgs {
-    const float* lg; const float* rg; const float* lc; const float* rc;
-    float* vol;
-    int B, C, Cc, H, W, D, G, K;
-    int VC, coff;
-    int mask_left;
-};
-
-__global__ __launch_bounds__(256) void build_volume_ncdhw_kernel(const VolNArgs p) {
+__global__ __launch_bounds__(256) void build_volume_ncdhw_kernel(const VolArgs p) {
     const int c = blockIdx.y;
     const int bd = blockIdx.z;
     const int b = bd / p.D, d = bd - b * p.D;
@@ -725,11 +629,20 @@ extern "C" int osa_pair_volume_f32(const float* left, const float* right, float*
     return 0;
 }
 
-static int build_volume_impl(const float* left_gwc, const float* right_gwc, int C, int num_groups, int gwc_stride,
-                             const float* left_cat, const float* right_cat, int Cc, int cat_stride,
-                             float* vol, int layout, int vol_channels, int c_off,
-                             int B, int H, int W, int maxdisp, int mask_left_concat, void* stream, float* vol_meta = nullptr,
-                             int split = 0, const float* gwc_meta = nullptr, const float* cat_meta = nullptr);
+// ------------------------------------------------------------------ launcher of the fused volume ----
+// f(std::integral_constant) of the first of V0, Vs... that equals v, of the last one otherwise (the idiom of mr_dispatch, mr_volume.h)
+template <int V0, int... Vs, class F>
+static inline void pick(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V0>{});
+    else if (v == V0) f(std::integral_constant<int, V0>{});
+    else pick<Vs...>(v, f);
+}
+// launch with `lds` bytes of dynamic LDS; above the default 64 KiB the kernel's limit is raised first
+template <class A>
+static inline void launch_lds(void (*kernel)(A), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A& a) {
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, a);
+}
 
 // d-walking form of the NDHWC builder (build_volume_walk_kernel): disparities per step (4 or 8), 0 = the chunked kernel
 static int g_vol_walk_ds = 8;
@@ -737,74 +650,103 @@ static int g_vol_walk_ds = 8;
 // the sub-batch of the default line: 0.466-0.506 -> 0.418-0.424 ms, whole model +0.7 % (profiles/round4/volume_walk_step_split.txt); the fp32
 // kernel is indifferent at 3 pairs and 2-3 % better with 8 at 8 pairs.
 static int g_vol_walk_split_ds = 4;
+static long long g_vol_walk_launches = 0;
+
+// the quad-lane kernels' precondition: whole quads of groups and of concat channels, a power of two of them per voxel, 16-byte stores
+static bool quads_eligible(int G, int Cc, const float* vol, int vol_channels, int c_off) {
+    const int nq4 = (G + 2 * Cc) / 4;
+    return (G % 4 == 0) && (Cc % 4 == 0) && nq4 >= 1 && nq4 <= 64 && (nq4 & (nq4 - 1)) == 0 && (vol_channels % 4 == 0) && (c_off % 4 == 0) &&
+           (((size_t)vol & 15) == 0);
+}
 static bool walk_eligible(int G, int K, int Cc, int gwc_stride, int cat_stride, const float* left_cat, const float* right_cat,
                           const float* vol, int vol_channels, int c_off, int W, int maxdisp, int ds) {
-    const int nch = G + 2 * Cc, nq4 = nch / 4;
     if (!(G == 0 || (K % 4 == 0 && K / 4 <= 4))) return false;
-    if (!((G % 4 == 0) && (Cc % 4 == 0) && nq4 >= 1 && nq4 <= 64 && (nq4 & (nq4 - 1)) == 0 && (vol_channels % 4 == 0) && (c_off % 4 == 0) &&
-          (((size_t)vol & 15) == 0))) return false;
-    const int WT = 8 * (64 / nq4);
+    if (!quads_eligible(G, Cc, vol, vol_channels, c_off)) return false;
+    const int WT = 8 * (64 / ((G + 2 * Cc) / 4));
     if (W < 2 * WT) return false;                                   // 8-wave pixel tiles
     if (!(G == 0 || gwc_stride > 0)) return false;
     if (!(Cc == 0 || (cat_stride > 0 && cat_stride % 4 == 0 && ((size_t)left_cat & 15) == 0 && ((size_t)right_cat & 15) == 0))) return false;
     return ds > 0 && WT % ds == 0 && maxdisp > ds;
 }
-static long long g_vol_walk_launches = 0;
-extern "C" int osa_volume_walk_step(int ds) {
-    const int prev = g_vol_walk_ds;
-    if (ds == 0 || ds == 4 || ds == 8) { g_vol_walk_ds = ds; g_vol_walk_split_ds = ds ? ds : 4; }     // (0: the fp32 output falls back to the chunked kernel; the split form exists as a walk only)
-    return prev;
-}
-extern "C" long long osa_volume_walk_launches(void) { return g_vol_walk_launches; }
 
-extern "C" int osa_build_volume_f32(const float* left_gwc, const float* right_gwc, int C, int num_groups,
-                                    const float* left_cat, const float* right_cat, int Cc,
-                                    float* vol, int layout, int vol_channels, int c_off,
-                                    int B, int H, int W, int maxdisp, int mask_left_concat,
-                                    float* vol_meta, void* stream) {
-    return build_volume_impl(left_gwc, right_gwc, C, num_groups, 0, left_cat, right_cat, Cc, 0, vol, layout,
-                             vol_channels, c_off, B, H, W, maxdisp, mask_left_concat, stream, vol_meta);
-}
-
-extern "C" int osa_build_volume_nhwc_f32(const float* left_gwc, const float* right_gwc, int C, int num_groups, int gwc_stride,
-                                         const float* left_cat, const float* right_cat, int Cc, int cat_stride,
-                                         float* vol, int vol_channels, int c_off,
-                                         int B, int H, int W, int maxdisp, int mask_left_concat, float* vol_meta, void* stream) {
-    OSA_REQUIRE((C == 0 || (gwc_stride >= C && gwc_stride % 4 == 0 && ((size_t)left_gwc & 15) == 0 && ((size_t)right_gwc & 15) == 0)),
-                "build_volume_nhwc: gwc features need stride >= C, stride %% 4 == 0 and 16-byte alignment");
-    OSA_REQUIRE((Cc == 0 || cat_stride >= Cc), "build_volume_nhwc: concat stride %d < Cc %d", cat_stride, Cc);
-    OSA_REQUIRE(C == 0 || (C / (num_groups > 0 ? num_groups : 1)) % 4 == 0, "build_volume_nhwc: channels per group must be a multiple of 4");
-    return build_volume_impl(left_gwc, right_gwc, C, num_groups, gwc_stride ? gwc_stride : C, left_cat, right_cat, Cc,
-                             cat_stride ? cat_stride : Cc, vol, OSA_NDHWC, vol_channels, c_off, B, H, W, maxdisp,
-                             mask_left_concat, stream, vol_meta);
+static int launch_walk(VolQArgs qa, int DS, hipStream_t st) {
+    VolArgs& a = qa.v;
+    const int WT = 8 * (64 / qa.NQ);
+    a.nWt = cdiv(a.W, WT); a.nDch = 1;
+    qa.DCH = DS;
+    const size_t wlds = (size_t)(WT / DS + 2) * DS * qa.RSq * 16 + 64;
+    const long long wblk = (long long)a.B * a.H * a.nWt;
+    OSA_REQUIRE(wlds <= 160 * 1024 && wblk < (1ll << 31), "build_volume: walk form does not fit (%zu B of LDS)", wlds);
+    pick<1, 2, 3, 4>(a.G > 0 ? a.K / 4 : 1, [&](auto qg) {
+        pick<4, 8>(DS, [&](auto ds) {
+            pick<1, 0>(qa.split ? 1 : 0, [&](auto sp) {
+                launch_lds(build_volume_walk_kernel<decltype(qg)::value, 8, decltype(ds)::value, decltype(sp)::value != 0>,
+                           dim3((unsigned)wblk), dim3(9 * 64), wlds, st, qa);
+            });
+        });
+    });
+    OSA_LAUNCH_CHECK("build_volume_walk");
+    ++g_vol_walk_launches;
+    return 0;
 }
 
-extern "C" int osa_build_volume_nhwc_split_eligible(const float* left_cat, const float* right_cat, const float* vol, int C, int num_groups,
-                                                    int gwc_stride, int Cc, int cat_stride, int vol_channels, int c_off, int W, int maxdisp) {
-    const int G = (C > 0) ? num_groups : 0;
-    if (C > 0 && (num_groups <= 0 || C % num_groups)) return 0;
-    const int K = G ? C / G : 0;
-    if (vol_channels % 16 || c_off % 16 || (G + 2 * Cc) % 16) return 0;
-    return walk_eligible(G, K, Cc, gwc_stride ? gwc_stride : C, cat_stride ? cat_stride : Cc, left_cat, right_cat, vol, vol_channels, c_off, W, maxdisp,
-                         g_vol_walk_split_ds) ? 1 : 0;
+// chunk plan of the chunked quad-lane kernel: D split evenly into the fewest chunks whose right window fits ~52 KiB of LDS (3 workgroups
+// of 4 waves per CU; 78 KiB for 2 of 8 waves); very wide feature vectors may use up to the whole 160 KiB.  Fills DCH, nWt, nDch.
+static int plan_quads(VolQArgs& qa, int nwv, size_t* lds) {
+    VolArgs& a = qa.v;
+    const int WT = nwv * (64 / qa.NQ);
+    const size_t budget = (nwv == 8) ? 78 * 1024 : 52 * 1024;
+    int nchunk = 1;
+    while (nchunk < a.D && (size_t)(WT + cdiv(a.D, nchunk) - 1) * qa.RSq * 16 > budget) ++nchunk;
+    qa.DCH = cdiv(a.D, nchunk);
+    a.nWt = cdiv(a.W, WT); a.nDch = cdiv(a.D, qa.DCH);
+    *lds = (size_t)(WT + qa.DCH - 1) * qa.RSq * 16;
+    OSA_REQUIRE(*lds <= 160 * 1024, "build_volume: %zu B of LDS needed (> 160 KiB); too many channels", *lds);
+    OSA_REQUIRE((long long)a.B * a.H * a.nWt * a.nDch < (1ll << 31), "build_volume: grid too large");
+    return 0;
+}
+static int launch_quads(const VolQArgs& qa, int nwv, size_t lds, hipStream_t st) {
+    const VolArgs& a = qa.v;
+    const dim3 grid((unsigned)((long long)a.B * a.H * a.nWt * a.nDch)), block(nwv * 64);
+    pick<1, 2, 3, 4>(a.G > 0 ? a.K / 4 : 1, [&](auto qg) {
+        pick<8, 4>(nwv, [&](auto nw) {
+            launch_lds(build_volume_quads_kernel<decltype(qg)::value, decltype(nw)::value>, grid, block, lds, st, qa);
+        });
+    });
+    OSA_LAUNCH_CHECK("build_volume_quads");
+    return 0;
 }
 
-extern "C" int osa_build_volume_nhwc_split_f16x3(const float* left_gwc, const float* right_gwc, int C, int num_groups, int gwc_stride,
-                                                 const float* left_cat, const float* right_cat, int Cc, int cat_stride,
-                                                 float* vol, int vol_channels, int c_off,
-                                                 int B, int H, int W, int maxdisp, int mask_left_concat,
-                                                 const float* gwc_meta, const float* cat_meta, float* vol_meta, void* stream) {
-    OSA_REQUIRE(vol_meta != nullptr && (C == 0 || gwc_meta != nullptr) && (Cc == 0 || cat_meta != nullptr),
-                "build_volume_nhwc_split: the range blocks of the features and of the volume are required (the scale of the split halves is derived from them)");
-    OSA_REQUIRE((C == 0 || (gwc_stride >= C && gwc_stride % 4 == 0 && ((size_t)left_gwc & 15) == 0 && ((size_t)right_gwc & 15) == 0)),
-                "build_volume_nhwc_split: gwc features need stride >= C, stride %% 4 == 0 and 16-byte alignment");
-    OSA_REQUIRE((Cc == 0 || cat_stride >= Cc), "build_volume_nhwc_split: concat stride %d < Cc %d", cat_stride, Cc);
-    OSA_REQUIRE(C == 0 || (C / (num_groups > 0 ? num_groups : 1)) % 4 == 0, "build_volume_nhwc_split: channels per group must be a multiple of 4");
-    return build_volume_impl(left_gwc, right_gwc, C, num_groups, gwc_stride ? gwc_stride : C, left_cat, right_cat, Cc,
-                             cat_stride ? cat_stride : Cc, vol, OSA_NDHWC, vol_channels, c_off, B, H, W, maxdisp,
-                             mask_left_concat, stream, vol_meta, 1, gwc_meta, cat_meta);
+static int launch_perchannel(VolArgs a, hipStream_t st) {
+    const int QG = (a.G > 0) ? a.K / 4 : 1;
+    const int gfl = (a.G > 0) ? QG * a.G * 4 : 0;
+    a.catbase = gfl;
+    int rs = gfl + ((a.Cc + 3) / 4) * 4;
+    if (((rs / 4) & 1) == 0) rs += 4;   // row stride / 16B odd -> conflict-free ds_write_b128 staging
+    a.RS = rs;
+    a.nWt = cdiv(a.W, VOL_WT); a.nDch = cdiv(a.D, VOL_DCH);
+    const size_t lds = (size_t)(VOL_WT + VOL_WT + VOL_DCH - 1) * rs * sizeof(float);
+    OSA_REQUIRE(lds <= 160 * 1024, "build_volume: %zu B of LDS needed (> 160 KiB); too many channels", lds);
+    const long long nblk = (long long)a.B * a.H * a.nWt * a.nDch;
+    OSA_REQUIRE(nblk < (1ll << 31), "build_volume: grid too large");
+    pick<1, 2, 3, 4>(QG, [&](auto qg) {
+        launch_lds(build_volume_ndhwc_kernel<decltype(qg)::value>, dim3((unsigned)nblk), dim3(256), lds, st, a);
+    });
+    OSA_LAUNCH_CHECK("build_volume_ndhwc");
+    return 0;
 }
 
+static int launch_ncdhw(const VolArgs& a, hipStream_t st) {
+    const int nch = a.G + 2 * a.Cc;
+    OSA_REQUIRE((long long)a.B * a.D <= 65535 && nch <= 65535, "build_volume: grid too large");
+    dim3 grid(cdiv((long long)a.H * a.W, 256), nch, a.B * a.D), block(256);
+    hipLaunchKernelGGL(build_volume_ncdhw_kernel, grid, block, 0, st, a);
+    OSA_LAUNCH_CHECK("build_volume_ncdhw");
+    return 0;
+}
+
+// Validates the arguments, fills the kernels' argument struct and chooses the kernel.  gwc_stride / cat_stride: 0 = NCHW features.
+// split != 0: the volume as a split tensor (osa_build_volume_nhwc_split_f16x3), scale from the features' range blocks gwc_meta / cat_meta.
 static int build_volume_impl(const float* left_gwc, const float* right_gwc, int C, int num_groups, int gwc_stride,
                              const float* left_cat, const float* right_cat, int Cc, int cat_stride,
                              float* vol, int layout, int vol_channels, int c_off,
@@ -827,159 +769,101 @@ static int build_volume_impl(const float* left_gwc, const float* right_gwc, int 
     OSA_REQUIRE(layout == OSA_NCDHW || layout == OSA_NDHWC, "build_volume: bad layout %d", layout);
     hipStream_t st = (hipStream_t)stream;
 
-    const bool fast = (layout == OSA_NDHWC) && (G == 0 || (K % 4 == 0 && K / 4 <= 4));
-    if (layout == OSA_NDHWC && !fast) {
+    VolQArgs qa{};
+    VolArgs& a = qa.v;
+    a.lg = left_gwc; a.rg = right_gwc; a.lc = left_cat; a.rc = right_cat; a.vol = vol; a.meta = vol_meta;
+    a.B = B; a.C = C; a.Cc = Cc; a.H = H; a.W = W; a.D = maxdisp; a.G = G; a.K = K;
+    a.VC = vol_channels; a.coff = c_off; a.mask_left = mask_left_concat;
+    a.gstride = gwc_stride; a.cstride = cat_stride;
+    qa.split = split; qa.gmeta = gwc_meta; qa.cmeta = cat_meta;
+
+    if (layout == OSA_NCDHW) {
+        OSA_REQUIRE(gwc_stride == 0 && cat_stride == 0, "build_volume: NHWC features need the NDHWC volume layout and K %% 4 == 0");
+        return launch_ncdhw(a, st);
+    }
+    if (!(G == 0 || (K % 4 == 0 && K / 4 <= 4))) {
         set_error("build_volume: NDHWC layout needs channels-per-group in {4,8,12,16} (got K=%d); "
                   "build NCDHW and convert with osa_ncdhw_to_ndhwc_f32", K);
         return -1;
     }
-    if (fast) {
-        const int nq4 = nch / 4;
-        const bool quads = (G % 4 == 0) && (Cc % 4 == 0) && nq4 >= 1 && nq4 <= 64 && (nq4 & (nq4 - 1)) == 0 &&
-                           (vol_channels % 4 == 0) && (c_off % 4 == 0) && (((size_t)vol & 15) == 0) &&
-                           !exp_set("OSA_VOL_PERCHANNEL");
-        if (quads) {
-            VolQArgs qa;
-            VolArgs& a = qa.v;
-            a.lg = left_gwc; a.rg = right_gwc; a.lc = left_cat; a.rc = right_cat; a.vol = vol; a.meta = vol_meta;
-            a.B = B; a.C = C; a.Cc = Cc; a.H = H; a.W = W; a.D = maxdisp; a.G = G; a.K = K;
-            a.VC = vol_channels; a.coff = c_off; a.mask_left = mask_left_concat;
-            a.gstride = gwc_stride; a.cstride = cat_stride;
-            a.RS = 0; a.catbase = 0;
-            const int QG = (G > 0) ? K / 4 : 1;
-            qa.NQ = nq4; qa.lgNQ = 0;
-            while ((1 << qa.lgNQ) < nq4) ++qa.lgNQ;
-            // 8 waves per workgroup when the map is wide enough (amortises the right window over 2x the pixels)
-            int nwv = (W >= 8 * (64 / nq4) * 2) ? 8 : 4;
-            { const int e = exp_int("OSA_VOL_WAVES", 0); if (e == 4 || e == 8) nwv = e; }
-            // two pixels per lane (PX2): the same pixel tile from half the waves
-            const bool px2 = exp_int("OSA_VOL_PX2", 0) != 0 && nwv == 8;
-            if (px2) nwv = 4;
-            const int WT = nwv * (64 / nq4) * (px2 ? 2 : 1);
-            qa.RSq = ((G > 0) ? QG * G : 0) + Cc / 4;
-            if (qa.RSq % 16 > 6) qa.RSq += 16 - qa.RSq % 16;     // keeps the lanes of two neighbouring voxels on distinct 16-byte slots
-            // disparity chunk: D split evenly into the fewest chunks whose right window fits ~52 KiB of
-            // LDS (3 workgroups per CU); very wide feature vectors may use up to the whole 160 KiB
-            size_t budget = (nwv == 8 || px2) ? 78 * 1024 : 52 * 1024;   // 2 x 8 waves (or 2 x 4 two-pixel waves) or 3 x 4 waves per CU
-            { const int e = exp_int("OSA_VOL_LDS", 0); if (e > 0) budget = (size_t)e; }
-            int nchunk = 1;
-            while (nchunk < maxdisp && (size_t)(WT + cdiv(maxdisp, nchunk) - 1) * qa.RSq * 16 > budget) ++nchunk;
-            const int dch = cdiv(maxdisp, nchunk);
-            qa.DCH = dch;
-            qa.dbg = exp_int("OSA_VOL_DBG", 0);
-            a.nWt = cdiv(W, WT); a.nDch = cdiv(maxdisp, dch);
-            const size_t lds = (size_t)(WT + dch - 1) * qa.RSq * 16;
-            OSA_REQUIRE(lds <= 160 * 1024, "build_volume: %zu B of LDS needed (> 160 KiB); too many channels", lds);
-            const long long nblk = (long long)B * H * a.nWt * a.nDch;
-            OSA_REQUIRE(nblk < (1ll << 31), "build_volume: grid too large");
-            dim3 grid((unsigned)nblk), block(nwv * 64);
-#define OSA_VOLQ_LAUNCH1(Q, NWV)                                                                    \
-            do {                                                                                    \
-                if (lds > 64 * 1024)                                                                \
-                    (void)hipFuncSetAttribute((const void*)build_volume_quads_kernel<Q, NWV>,       \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);\
-                hipLaunchKernelGGL((build_volume_quads_kernel<Q, NWV>), grid, block, lds, st, qa);  \
-            } while (0)
-#define OSA_VOLQ_LAUNCH1P(Q, NWV)                                                                   \
-            do {                                                                                    \
-                if (lds > 64 * 1024)                                                                \
-                    (void)hipFuncSetAttribute((const void*)build_volume_quads_kernel<Q, NWV, true>, \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);\
-                hipLaunchKernelGGL((build_volume_quads_kernel<Q, NWV, true>), grid, block, lds, st, qa); \
-            } while (0)
-#define OSA_VOLQ_LAUNCH(Q) do { if (px2) { if (nwv == 8) OSA_VOLQ_LAUNCH1P(Q, 8); else OSA_VOLQ_LAUNCH1P(Q, 4); }    \
-                                else if (nwv == 8) OSA_VOLQ_LAUNCH1(Q, 8); else OSA_VOLQ_LAUNCH1(Q, 4); } while (0)
-            // d-walking form (build_volume_walk_kernel): NHWC features with 16-byte aligned quads, 8-wave pixel tiles
-            const int walk_ds = split ? g_vol_walk_split_ds : g_vol_walk_ds;
-            const bool walk = !px2 && nwv == 8 && walk_eligible(G, K, Cc, gwc_stride, cat_stride, left_cat, right_cat, vol, vol_channels, c_off, W, maxdisp, walk_ds);
-            OSA_REQUIRE(!split || (walk && vol_channels % 16 == 0 && c_off % 16 == 0 && nch % 16 == 0),
-                        "build_volume: split output needs the d-walking form and 16-channel aligned volume channels (osa_build_volume_nhwc_split_eligible)");
-            qa.split = split; qa.gmeta = gwc_meta; qa.cmeta = cat_meta;
-            if (walk) {
-                const int DS = walk_ds;
-                a.nWt = cdiv(W, WT); a.nDch = 1;
-                qa.DCH = DS; qa.dbg = 0;
-                const size_t wlds = (size_t)(WT / DS + 2) * DS * qa.RSq * 16 + 64;
-                const long long wblk = (long long)B * H * a.nWt;
-                OSA_REQUIRE(wlds <= 160 * 1024 && wblk < (1ll << 31), "build_volume: walk form does not fit (%zu B of LDS)", wlds);
-#define OSA_VOLW_LAUNCH1(Q, DSV, SP)                                                                \
-                do {                                                                                \
-                    if (wlds > 64 * 1024)                                                           \
-                        (void)hipFuncSetAttribute((const void*)build_volume_walk_kernel<Q, 8, DSV, SP>, \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds); \
-                    hipLaunchKernelGGL((build_volume_walk_kernel<Q, 8, DSV, SP>), dim3((unsigned)wblk), dim3(9 * 64), wlds, st, qa); \
-                } while (0)
-#define OSA_VOLW_LAUNCH(Q) do { if (split) { if (DS == 4) OSA_VOLW_LAUNCH1(Q, 4, true); else OSA_VOLW_LAUNCH1(Q, 8, true); }   \
-                                else { if (DS == 4) OSA_VOLW_LAUNCH1(Q, 4, false); else OSA_VOLW_LAUNCH1(Q, 8, false); } } while (0)
-                switch (QG) {
-                    case 1: OSA_VOLW_LAUNCH(1); break;
-                    case 2: OSA_VOLW_LAUNCH(2); break;
-                    case 3: OSA_VOLW_LAUNCH(3); break;
-                    default: OSA_VOLW_LAUNCH(4); break;
-                }
-#undef OSA_VOLW_LAUNCH
-#undef OSA_VOLW_LAUNCH1
-                OSA_LAUNCH_CHECK("build_volume_walk");
-                ++g_vol_walk_launches;
-                return 0;
-            }
-            switch (QG) {
-                case 1: OSA_VOLQ_LAUNCH(1); break;
-                case 2: OSA_VOLQ_LAUNCH(2); break;
-                case 3: OSA_VOLQ_LAUNCH(3); break;
-                default: OSA_VOLQ_LAUNCH(4); break;
-            }
-#undef OSA_VOLQ_LAUNCH1
-#undef OSA_VOLQ_LAUNCH1P
-#undef OSA_VOLQ_LAUNCH
-            OSA_LAUNCH_CHECK("build_volume_quads");
-            return 0;
-        }
+    if (!quads_eligible(G, Cc, vol, vol_channels, c_off) || exp_set("OSA_VOL_PERCHANNEL")) {
         OSA_REQUIRE(!split, "build_volume: split output needs the quad-lane d-walking form (osa_build_volume_nhwc_split_eligible)");
-        VolArgs a;
-        a.lg = left_gwc; a.rg = right_gwc; a.lc = left_cat; a.rc = right_cat; a.vol = vol; a.meta = vol_meta;
-        a.B = B; a.C = C; a.Cc = Cc; a.H = H; a.W = W; a.D = maxdisp; a.G = G; a.K = K;
-        a.VC = vol_channels; a.coff = c_off; a.mask_left = mask_left_concat;
-        a.gstride = gwc_stride; a.cstride = cat_stride;
-        const int QG = (G > 0) ? K / 4 : 1;
-        const int gfl = (G > 0) ? QG * G * 4 : 0;
-        a.catbase = gfl;
-        int rs = gfl + ((Cc + 3) / 4) * 4;
-        if (((rs / 4) & 1) == 0) rs += 4;   // row stride / 16B odd -> conflict-free ds_write_b128 staging
-        a.RS = rs;
-        a.nWt = cdiv(W, VOL_WT); a.nDch = cdiv(maxdisp, VOL_DCH);
-        const size_t lds = (size_t)(VOL_WT + VOL_WT + VOL_DCH - 1) * rs * sizeof(float);
-        OSA_REQUIRE(lds <= 160 * 1024, "build_volume: %zu B of LDS needed (> 160 KiB); too many channels", lds);
-        const long long nblk = (long long)B * H * a.nWt * a.nDch;
-        OSA_REQUIRE(nblk < (1ll << 31), "build_volume: grid too large");
-        dim3 grid((unsigned)nblk), block(256);
-#define OSA_VOL_LAUNCH(Q)                                                                           \
-        do {                                                                                        \
-            if (lds > 64 * 1024)                                                                    \
-                (void)hipFuncSetAttribute((const void*)build_volume_ndhwc_kernel<Q>,                \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);    \
-            hipLaunchKernelGGL(build_volume_ndhwc_kernel<Q>, grid, block, lds, st, a);              \
-        } while (0)
-        switch (QG) {
-            case 1: OSA_VOL_LAUNCH(1); break;
-            case 2: OSA_VOL_LAUNCH(2); break;
-            case 3: OSA_VOL_LAUNCH(3); break;
-            default: OSA_VOL_LAUNCH(4); break;
-        }
-#undef OSA_VOL_LAUNCH
-        OSA_LAUNCH_CHECK("build_volume_ndhwc");
-        return 0;
+        return launch_perchannel(a, st);
     }
-    OSA_REQUIRE(gwc_stride == 0 && cat_stride == 0, "build_volume: NHWC features need the NDHWC volume layout and K %% 4 == 0");
-    VolNArgs a;
-    a.lg = left_gwc; a.rg = right_gwc; a.lc = left_cat; a.rc = right_cat; a.vol = vol;
-    a.B = B; a.C = C; a.Cc = Cc; a.H = H; a.W = W; a.D = maxdisp; a.G = G; a.K = K;
-    a.VC = vol_channels; a.coff = c_off; a.mask_left = mask_left_concat;
-    OSA_REQUIRE((long long)B * maxdisp <= 65535 && nch <= 65535, "build_volume: grid too large");
-    dim3 grid(cdiv((long long)H * W, 256), nch, B * maxdisp), block(256);
-    hipLaunchKernelGGL(build_volume_ncdhw_kernel, grid, block, 0, st, a);
-    OSA_LAUNCH_CHECK("build_volume_ncdhw");
+    const int nq4 = nch / 4;
+    qa.NQ = nq4; qa.lgNQ = 0;
+    while ((1 << qa.lgNQ) < nq4) ++qa.lgNQ;
+    qa.RSq = ((G > 0) ? (K / 4) * G : 0) + Cc / 4;
+    if (qa.RSq % 16 > 6) qa.RSq += 16 - qa.RSq % 16;     // keeps the lanes of two neighbouring voxels on distinct 16-byte slots
+    // 8 waves per workgroup when the map is wide enough (amortises the right window over 2x the pixels)
+    const int nwv = (W >= 8 * (64 / nq4) * 2) ? 8 : 4;
+    size_t lds;
+    if (int rc = plan_quads(qa, nwv, &lds)) return rc;
+    // d-walking form (build_volume_walk_kernel): NHWC features with 16-byte aligned quads, 8-wave pixel tiles
+    const int walk_ds = split ? g_vol_walk_split_ds : g_vol_walk_ds;
+    const bool walk = walk_eligible(G, K, Cc, gwc_stride, cat_stride, left_cat, right_cat, vol, vol_channels, c_off, W, maxdisp, walk_ds);
+    OSA_REQUIRE(!split || (walk && vol_channels % 16 == 0 && c_off % 16 == 0 && nch % 16 == 0),
+                "build_volume: split output needs the d-walking form and 16-channel aligned volume channels (osa_build_volume_nhwc_split_eligible)");
+    return walk ? launch_walk(qa, walk_ds, st) : launch_quads(qa, nwv, lds, st);
+}
+
+extern "C" int osa_volume_walk_step(int ds) {
+    const int prev = g_vol_walk_ds;
+    if (ds == 0 || ds == 4 || ds == 8) { g_vol_walk_ds = ds; g_vol_walk_split_ds = ds ? ds : 4; }     // (0: the fp32 output falls back to the chunked kernel; the split form exists as a walk only)
+    return prev;
+}
+extern "C" long long osa_volume_walk_launches(void) { return g_vol_walk_launches; }
+
+extern "C" int osa_build_volume_f32(const float* left_gwc, const float* right_gwc, int C, int num_groups,
+                                    const float* left_cat, const float* right_cat, int Cc,
+                                    float* vol, int layout, int vol_channels, int c_off,
+                                    int B, int H, int W, int maxdisp, int mask_left_concat,
+                                    float* vol_meta, void* stream) {
+    return build_volume_impl(left_gwc, right_gwc, C, num_groups, 0, left_cat, right_cat, Cc, 0, vol, layout,
+                             vol_channels, c_off, B, H, W, maxdisp, mask_left_concat, stream, vol_meta, 0, nullptr, nullptr);
+}
+
+// what the two NHWC entry points ask of their features; `who` is the prefix of the messages
+static int check_nhwc_features(const char* who, const float* left_gwc, const float* right_gwc, int C, int num_groups, int gwc_stride,
+                               int Cc, int cat_stride) {
+    OSA_REQUIRE((C == 0 || (gwc_stride >= C && gwc_stride % 4 == 0 && ((size_t)left_gwc & 15) == 0 && ((size_t)right_gwc & 15) == 0)),
+                "%s: gwc features need stride >= C, stride %% 4 == 0 and 16-byte alignment", who);
+    OSA_REQUIRE((Cc == 0 || cat_stride >= Cc), "%s: concat stride %d < Cc %d", who, cat_stride, Cc);
+    OSA_REQUIRE(C == 0 || (C / (num_groups > 0 ? num_groups : 1)) % 4 == 0, "%s: channels per group must be a multiple of 4", who);
     return 0;
+}
+
+extern "C" int osa_build_volume_nhwc_f32(const float* left_gwc, const float* right_gwc, int C, int num_groups, int gwc_stride,
+                                         const float* left_cat, const float* right_cat, int Cc, int cat_stride,
+                                         float* vol, int vol_channels, int c_off,
+                                         int B, int H, int W, int maxdisp, int mask_left_concat, float* vol_meta, void* stream) {
+    if (int rc = check_nhwc_features("build_volume_nhwc", left_gwc, right_gwc, C, num_groups, gwc_stride, Cc, cat_stride)) return rc;
+    return build_volume_impl(left_gwc, right_gwc, C, num_groups, gwc_stride ? gwc_stride : C, left_cat, right_cat, Cc,
+                             cat_stride ? cat_stride : Cc, vol, OSA_NDHWC, vol_channels, c_off, B, H, W, maxdisp,
+                             mask_left_concat, stream, vol_meta, 0, nullptr, nullptr);
+}
+
+extern "C" int osa_build_volume_nhwc_split_eligible(const float* left_cat, const float* right_cat, const float* vol, int C, int num_groups,
+                                                    int gwc_stride, int Cc, int cat_stride, int vol_channels, int c_off, int W, int maxdisp) {
+    const int G = (C > 0) ? num_groups : 0;
+    if (C > 0 && (num_groups <= 0 || C % num_groups)) return 0;
+    const int K = G ? C / G : 0;
+    if (vol_channels % 16 || c_off % 16 || (G + 2 * Cc) % 16) return 0;
+    return walk_eligible(G, K, Cc, gwc_stride ? gwc_stride : C, cat_stride ? cat_stride : Cc, left_cat, right_cat, vol, vol_channels, c_off, W, maxdisp,
+                         g_vol_walk_split_ds) ? 1 : 0;
+}
+
+extern "C" int osa_build_volume_nhwc_split_f16x3(const float* left_gwc, const float* right_gwc, int C, int num_groups, int gwc_stride,
+                                                 const float* left_cat, const float* right_cat, int Cc, int cat_stride,
+                                                 float* vol, int vol_channels, int c_off,
+                                                 int B, int H, int W, int maxdisp, int mask_left_concat,
+                                                 const float* gwc_meta, const float* cat_meta, float* vol_meta, void* stream) {
+    OSA_REQUIRE(vol_meta != nullptr && (C == 0 || gwc_meta != nullptr) && (Cc == 0 || cat_meta != nullptr),
+                "build_volume_nhwc_split: the range blocks of the features and of the volume are required (the scale of the split halves is derived from them)");
+    if (int rc = check_nhwc_features("build_volume_nhwc_split", left_gwc, right_gwc, C, num_groups, gwc_stride, Cc, cat_stride)) return rc;
+    return build_volume_impl(left_gwc, right_gwc, C, num_groups, gwc_stride ? gwc_stride : C, left_cat, right_cat, Cc,
+                             cat_stride ? cat_stride : Cc, vol, OSA_NDHWC, vol_channels, c_off, B, H, W, maxdisp,
+                             mask_left_concat, stream, vol_meta, 1, gwc_meta, cat_meta);
 }
 
 extern "C" int osa_corr_volume_f32(const float* left, const float* right, float* vol,

@@ -50,15 +50,17 @@ def test_volume_functions_vs_reference_golden(tag):
     close(ops.to_ncdhw(v, ref.shape[1]), ref, what="fused NDHWC volume via layout kernel")
 
 
-def test_volume_gwcnet_shape_vs_oracle():
-    """GwcNet channel configuration (320ch/40 groups + 12 concat) on a short row block."""
+@pytest.mark.parametrize("W, D", [(50, 48), (70, 24)])
+def test_volume_gwcnet_shape_vs_oracle(W, D):
+    """GwcNet channel configuration (320ch/40 groups + 12 concat) on a short row block, NCHW features: W = 50 takes the 4-wave chunked
+    quad-lane kernel, W = 70 (two 32-pixel tiles and a ragged third) the 8-wave one."""
     from openstereo_amd import ops
     from oracle import torch_ref as O
     rng = np.random.default_rng(5)
-    lg, rg = (T(rng.normal(0, 1, (1, 320, 3, 50)).astype(np.float32)) for _ in range(2))
-    lc, rc = (T(rng.normal(0, 1, (1, 12, 3, 50)).astype(np.float32)) for _ in range(2))
-    ref = torch.cat((O.gwc_volume(lg, rg, 48, 40), O.concat_volume(lc, rc, 48)), 1)
-    v = ops.build_cost_volume_cl(g2(lg), g2(rg), 40, g2(lc), g2(rc), maxdisp=48)
+    lg, rg = (T(rng.normal(0, 1, (1, 320, 3, W)).astype(np.float32)) for _ in range(2))
+    lc, rc = (T(rng.normal(0, 1, (1, 12, 3, W)).astype(np.float32)) for _ in range(2))
+    ref = torch.cat((O.gwc_volume(lg, rg, D, 40), O.concat_volume(lc, rc, D)), 1)
+    v = ops.build_cost_volume_cl(g2(lg), g2(rg), 40, g2(lc), g2(rc), maxdisp=D)
     assert v.shape == ref.shape and ops.is_cl(v)
     close(v, ref, atol=2e-6, rtol=1e-5, what="gwcnet fused volume")
 
@@ -1060,6 +1062,20 @@ def test_conv_b_ring_is_bit_identical(case, prec):
 
 
 # ----------------------------------------------------------------------------- d-walking volume builder (r4)
+WALK_K12 = ("K = 12", 1, 96, 8, 12, 3, 130, 19, True)               # 3 float4s per group, 8 quads per voxel: 64-pixel tiles
+WALK_K16 = ("K = 16", 1, 128, 8, 4, 2, 260, 11, True)               # 4 float4s per group, 4 quads per voxel: 128-pixel tiles
+
+
+def _walk_features(case):
+    """The channels-last feature pair of a walking-form case (left images first), seeded."""
+    from openstereo_amd import ops
+    _, B, C, _, Cc, H, W, _, _ = case
+    rng = np.random.default_rng(5)
+    gf = ops.empty_cl(2 * B, max(C, 4), 1, H, W, DEV); gf.copy_(T(rng.normal(0, 1, tuple(gf.shape)).astype(np.float32)))
+    cf = ops.empty_cl(2 * B, Cc, 1, H, W, DEV); cf.copy_(T(rng.normal(0, 1, tuple(cf.shape)).astype(np.float32)))
+    return gf, cf
+
+
 @pytest.mark.parametrize("step", [8, 4])
 @pytest.mark.parametrize("case", [
     # name, B, gwc channels, groups, concat channels, H, W, D, mask_left
@@ -1069,6 +1085,8 @@ def test_conv_b_ring_is_bit_identical(case, prec):
     ("unmasked concat", 1, 320, 40, 12, 4, 80, 24, False),          # IGEV-style copy (left concat not masked)
     ("K = 4", 1, 64, 16, 8, 6, 140, 17, True),                       # 4 + 4 quads = 8 per voxel: 64-pixel tiles
     ("concat only", 1, 0, 0, 16, 4, 130, 12, True),
+    WALK_K12,
+    WALK_K16,
 ], ids=lambda c: c[0])
 def test_volume_walking_form_is_bit_identical(case, step):
     """csrc/volume.hip build_volume_walk_kernel (a workgroup walks along d, right window as an LDS ring refilled by a loader wave through
@@ -1076,9 +1094,7 @@ def test_volume_walking_form_is_bit_identical(case, step):
     from openstereo_amd import _lib, ops, ranges
     lib = _lib.load()
     name, B, C, G, Cc, H, W, D, mask_left = case
-    rng = np.random.default_rng(5)
-    gf = ops.empty_cl(2 * B, max(C, 4), 1, H, W, DEV); gf.copy_(T(rng.normal(0, 1, tuple(gf.shape)).astype(np.float32)))
-    cf = ops.empty_cl(2 * B, Cc, 1, H, W, DEV); cf.copy_(T(rng.normal(0, 1, tuple(cf.shape)).astype(np.float32)))
+    gf, cf = _walk_features(case)
     run = lambda: ops.build_cost_volume_from_cl(gf, G, cf, B, D, gwc_channels=C, mask_left=mask_left)
     prev = lib.osa_volume_walk_step(0)
     try:
@@ -1093,6 +1109,24 @@ def test_volume_walking_form_is_bit_identical(case, step):
     torch.cuda.synchronize()
     assert torch.equal(v_chunk, v_walk), f"{name}: walking form differs by {(v_chunk - v_walk).abs().max().item():.3e}"
     assert float(ranges.meta_of(v_walk)[::16][:8].max()) == float(v_walk.abs().max()) == float(ranges.meta_of(v_chunk)[::16][:8].max())
+
+
+@pytest.mark.parametrize("case", [WALK_K12, WALK_K16], ids=lambda c: c[0])
+def test_volume_wide_groups_vs_oracle(case):
+    """12 and 16 channels per group through the quad-lane kernels (default walking step) against the CPU oracle: bit identity of the
+    walking and the chunked form would not see an error common to both.  Tolerance of test_volume_gwcnet_shape_vs_oracle."""
+    from openstereo_amd import _lib, ops
+    from oracle import torch_ref as O
+    lib = _lib.load()
+    name, B, C, G, Cc, H, W, D, mask_left = case
+    gf, cf = _walk_features(case)
+    n0 = lib.osa_volume_walk_launches()
+    v = ops.build_cost_volume_from_cl(gf, G, cf, B, D, gwc_channels=C, mask_left=mask_left)
+    assert lib.osa_volume_walk_launches() == n0 + 1, "the walking form did not run"
+    lg, rg, lc, rc = (t.cpu().contiguous() for t in (gf[:B, :C, 0], gf[B:, :C, 0], cf[:B, :Cc, 0], cf[B:, :Cc, 0]))
+    ref = torch.cat((O.gwc_volume(lg, rg, D, G), O.concat_volume(lc, rc, D)), 1)
+    assert ops.is_cl(v)
+    close(v[:, :ref.shape[1]], ref, atol=2e-6, rtol=1e-5, what=f"{name}: fused volume")
 
 
 @pytest.mark.parametrize("case", [("gwcnet", 2, 320, 40, 12, 9, 96, 48), ("gwcnet ragged", 1, 320, 40, 12, 5, 75, 21), ("concat only", 1, 0, 0, 16, 4, 130, 12)],
