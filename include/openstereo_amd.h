@@ -34,6 +34,7 @@
  *                               models/psmnet/psmnet_cost_processor.py:201-214
  *   osa_*softargmin_var_f32     the three heads with disparity_variance beside the disparity,
  *                               models/cfnet/submodule.py:128-134, models/igevpp/submodule.py:153-159
+ *   osa_mv2_block3d_f32         MobileStereoNet's 3-D inverted-residual block in eval mode, models/msnet/submodule.py:136-173
  *   osa_geo_lookup_mr_*_f32     the multi-range lookup of IGEV++'s GRU loop (three geometry volumes of different disparity
  *                               ranges + the correlation pyramid -> four tensors), models/igevpp/geometry.py:6-87
  */
@@ -46,7 +47,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 11
+#define OSA_ABI_VERSION 12
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -659,6 +660,23 @@ int osa_geo_lookup_mr_bwd_acc_f32(float* const* dgeo0_levels, float* const* dcor
                                   const float* disp, const float* coords_x,
                                   const float* dfeat0, const float* dfeat1, const float* dfeat2, const float* dcorr_out,
                                   int B, int H, int W, int C, int radius, void* stream);
+
+/* ---- MobileStereoNet's 3-D inverted-residual block (models/msnet/submodule.py:136-173, MobileV2_Residual_3D), ABI 12 ----
+ * Eval mode, ONE launch (csrc/mv2_block3d.hip):  y = bn3(W3 relu6(bn2(dw3x3x3(relu6(bn1(W1 x)))))) (+ x when residual)
+ * with a 1x1x1 expansion Ci -> Ch, a depthwise 3x3x3 convolution of stride 1 or 2 and padding 1 (zeros around the HIDDEN tensor) and a
+ * 1x1x1 projection Ch -> Co.  x [B,D,H,W,Ci] and y [B,Do,Ho,Wo,Co] are fp32 NDHWC, Do = (D - 1) / stride + 1 and likewise Ho, Wo; the
+ * hidden tensors never reach memory.  Exact fp32 in every arithmetic mode, no atomics, bit-reproducible, independent of the batch size.
+ * Supported: Ci, Ch, Co multiples of 8, Ci and Co <= 128, Ch <= 256, stride 1 or 2, any B, D, H, W >= 1 with fewer than 2^31 elements in
+ * x and in y; residual needs stride 1 and Ci == Co.
+ * osa_mv2_block3d_pack_f32: the three weights in the reference's layouts (w_expand [Ch,Ci,1,1,1], w_dw [Ch,1,3,3,3], w_project
+ * [Co,Ch,1,1,1]) and the three folded BatchNorms (y = x * scale + shift, per channel) -> `packed`, osa_mv2_block3d_packed_floats(Ci, Ch, Co)
+ * floats (0 for non-positive arguments), in one small launch. */
+size_t osa_mv2_block3d_packed_floats(int Ci, int Ch, int Co);
+int osa_mv2_block3d_pack_f32(const float* w_expand, const float* w_dw, const float* w_project, const float* scale1, const float* shift1,
+                             const float* scale2, const float* shift2, const float* scale3, const float* shift3, float* packed,
+                             int Ci, int Ch, int Co, void* stream);
+int osa_mv2_block3d_f32(const float* x, const float* packed, float* y, int B, int D, int H, int W, int Ci, int Ch, int Co, int stride, int residual,
+                        void* stream);
 
 /* ---- input pre-processing on device ------------------------- */
 /* RightTopPad(edge) + HWC->CHW + /255 + (x-mean)/std for the left and right image in one launch

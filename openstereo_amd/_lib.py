@@ -152,6 +152,9 @@ SIGNATURES = {
     "osa_mr_volume_f32": (c_i, [c_fp] * 7 + [c_i] * 12 + [c_st]),
     "osa_mr_volume_bwd_workspace_bytes": (C.c_size_t, [c_i] * 4),
     "osa_mr_volume_bwd_ws_f32": (c_i, [c_fp] * 3 + [c_i] + [c_fp] * 8 + [c_i] * 11 + [c_fp, C.c_size_t, c_st]),
+    "osa_mv2_block3d_packed_floats": (C.c_size_t, [c_i] * 3),
+    "osa_mv2_block3d_pack_f32": (c_i, [c_fp] * 10 + [c_i] * 3 + [c_st]),
+    "osa_mv2_block3d_f32": (c_i, [c_fp] * 3 + [c_i] * 9 + [c_st]),
 }
 
 

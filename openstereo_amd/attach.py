@@ -218,7 +218,7 @@ M = "stereo.modeling.models."
 
 
 def _graft_plan():
-    from .models import gwcnet as GW, psmnet as PSM, igev_style as IG, lightstereo as LS, igev_update as UP
+    from .models import gwcnet as GW, psmnet as PSM, igev_style as IG, lightstereo as LS, igev_update as UP, msnet as MS
     fwd = ("forward", "forward_cl", "forward_train", "_pack", "reset_engine")
     gru = ("_packs", "new_level", "step", "_levels")          # per-level state buffers of the update block (igev_update.py)
     return [
@@ -240,6 +240,7 @@ def _graft_plan():
         (M + "igev.submodule", {"FeatureAtt": (IG.IGEVFeatureAtt, ("logits",), False)}),
         (M + "igev.igev_stereo", {"hourglass": (IG.hourglass, ("forward", "forward_cl", "forward_train", "_unit_train", "_packed_layers", "reset_engine"), False)}),  # :51-76
         (M + "lightstereo.aggregation", {c: (getattr(LS, c), fwd, False) for c in ("Aggregation", "MobileV2Residual", "AttentionModule")}),
+        (M + "msnet.submodule", {"MobileV2_Residual_3D": (MS.MobileV2Residual3D, ("forward", "reset_engine"), True)}),   # submodule.py:136-173: eval mode only
         (M + "igev.update", {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}),
         (M + "stereobase.gru_blocks", {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}),
     ]

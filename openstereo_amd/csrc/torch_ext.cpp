@@ -129,6 +129,57 @@ Tensor4 mr_volume_bwd(const OptTensor& dv0, const OptTensor& dv1, const OptTenso
     return out;
 }
 
+// MobileStereoNet's 3-D inverted-residual block in eval mode (models/msnet/submodule.py:136-173; csrc/mv2_block3d.hip).  An inference op:
+// no Autograd kernel (attach keeps the reference's forward in training mode and whenever a gradient is required).
+struct Mv2Dims { int Ci, Ch, Co; };
+static Mv2Dims mv2_pack_dims(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, at::TensorList bn) {
+    TORCH_CHECK(w1.dim() == 5 && wd.dim() == 5 && w3.dim() == 5 && w1.sizes().slice(2) == at::IntArrayRef({1, 1, 1}) && w3.sizes().slice(2) == at::IntArrayRef({1, 1, 1}) &&
+                wd.sizes().slice(1) == at::IntArrayRef({1, 3, 3, 3}) && wd.size(0) == w1.size(0) && w3.size(1) == w1.size(0),
+                "mv2_block3d_pack: weights must be [Ch,Ci,1,1,1], [Ch,1,3,3,3] and [Co,Ch,1,1,1]");
+    const int64_t n[6] = {w1.size(0), w1.size(0), w1.size(0), w1.size(0), w3.size(0), w3.size(0)};
+    for (int i = 0; i < 6; ++i)
+        TORCH_CHECK(bn[i].dim() == 1 && bn[i].size(0) == n[i], "mv2_block3d_pack: folded BatchNorm vector ", i, " has shape ", bn[i].sizes(), ", expected [", n[i], "]");
+    return {(int)w1.size(1), (int)w1.size(0), (int)w3.size(0)};
+}
+at::Tensor mv2_block3d_pack_meta(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2,
+                                 const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
+    const Mv2Dims d = mv2_pack_dims(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
+    return at::empty({(int64_t)osa_mv2_block3d_packed_floats(d.Ci, d.Ch, d.Co)}, w1.options().dtype(at::kFloat));
+}
+at::Tensor mv2_block3d_pack(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2,
+                            const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
+    at::Tensor t[9];
+    int i = 0;
+    for (const at::Tensor* s : {&w1, &wd, &w3, &s1, &b1, &s2, &b2, &s3, &b3}) t[i++] = gpu_f32(*s, "mv2_block3d_pack argument").detach().contiguous();
+    const Mv2Dims d = mv2_pack_dims(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
+    auto packed = mv2_block3d_pack_meta(w1, wd, w3, s1, b1, s2, b2, s3, b3);
+    OSA_CALL(osa_mv2_block3d_pack_f32(fp(t[0]), fp(t[1]), fp(t[2]), fp(t[3]), fp(t[4]), fp(t[5]), fp(t[6]), fp(t[7]), fp(t[8]), packed.data_ptr<float>(), d.Ci, d.Ch, d.Co, cur_stream()));
+    return packed;
+}
+// -> logical [B, Co, Do, Ho, Wo] with channels_last_3d strides
+at::Tensor mv2_block3d_meta(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t stride, bool residual) {
+    TORCH_CHECK(x.dim() == 5, "mv2_block3d: x must be [B,Ci,D,H,W], got ", x.sizes());
+    TORCH_CHECK(stride == 1 || stride == 2, "mv2_block3d: stride ", stride, " (supported: 1 and 2)");
+    TORCH_CHECK(Ch > 0 && Co > 0 && packed.dim() == 1 && packed.size(0) == (int64_t)osa_mv2_block3d_packed_floats((int)x.size(1), (int)Ch, (int)Co),
+                "mv2_block3d: packed parameters of ", packed.numel(), " floats do not belong to channels ", x.size(1), " -> ", Ch, " -> ", Co);
+    TORCH_CHECK(!residual || (stride == 1 && x.size(1) == Co), "mv2_block3d: residual needs stride 1 and equal channels");
+    auto out = [&](int64_t n) { return (n - 1) / stride + 1; };
+    return mr_empty(x, x.size(0), Co, out(x.size(2)), out(x.size(3)), out(x.size(4)), true);
+}
+at::Tensor mv2_block3d(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t stride, bool residual) {
+    gpu_f32(x, "x"); gpu_f32(packed, "packed");
+    auto y = mv2_block3d_meta(x, packed, Ch, Co, stride, residual);
+    const int64_t B = x.size(0), Ci = x.size(1), D = x.size(2), H = x.size(3), W = x.size(4);
+    at::Tensor xc = x;                                       // a dense channels_last_3d x is read in place
+    if (!x.is_contiguous(at::MemoryFormat::ChannelsLast3d)) {
+        xc = mr_empty(x, B, Ci, D, H, W, true);
+        const auto xn = x.contiguous();
+        OSA_CALL(osa_ncdhw_to_ndhwc_f32(fp(xn), xc.data_ptr<float>(), (int)B, (int)Ci, (long long)(D * H * W), (int)Ci, 0, cur_stream()));
+    }
+    OSA_CALL(osa_mv2_block3d_f32(fp(xc), fp(packed), y.data_ptr<float>(), (int)B, (int)D, (int)H, (int)W, (int)Ci, (int)Ch, (int)Co, (int)stride, residual ? 1 : 0, cur_stream()));
+    return y;
+}
+
 // ---- regression heads ----------------------------------------------------------------------------------------------------------
 at::Tensor softargmin(const at::Tensor& prob) {
     gpu_f32(prob, "prob");
@@ -1223,6 +1274,8 @@ TORCH_LIBRARY(osa_native, m) {
     m.def("abi_version() -> int", &abi_version);
     m.def("gwc_volume(Tensor left, Tensor right, int maxdisp, int groups) -> Tensor");
     m.def("mr_volume(Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last=False) -> (Tensor, Tensor, Tensor)");
+    m.def("mv2_block3d_pack(Tensor w_expand, Tensor w_dw, Tensor w_project, Tensor scale1, Tensor shift1, Tensor scale2, Tensor shift2, Tensor scale3, Tensor shift3) -> Tensor");
+    m.def("mv2_block3d(Tensor x, Tensor packed, int hidden, int out_channels, int stride, bool residual) -> Tensor");
     m.def("mr_volume_bwd(Tensor? dv0, Tensor? dv1, Tensor? dv2, Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("concat_volume(Tensor left, Tensor right, int maxdisp, bool mask_left=True) -> Tensor");
     m.def("corr_volume(Tensor left, Tensor right, int maxdisp) -> Tensor");
@@ -1294,6 +1347,8 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
     m.impl("gwc_volume", &gwc_volume);
     m.impl("mr_volume", &mr_volume);
     m.impl("mr_volume_bwd", &mr_volume_bwd);
+    m.impl("mv2_block3d_pack", &mv2_block3d_pack);
+    m.impl("mv2_block3d", &mv2_block3d);
     m.impl("concat_volume", &concat_volume);
     m.impl("corr_volume", &corr_volume);
     m.impl("softargmin", &softargmin);
@@ -1357,6 +1412,8 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
     m.impl("gwc_volume", &gwc_volume_meta);
     m.impl("mr_volume", &mr_volume_meta);
     m.impl("mr_volume_bwd", &mr_volume_bwd_meta);
+    m.impl("mv2_block3d_pack", &mv2_block3d_pack_meta);
+    m.impl("mv2_block3d", &mv2_block3d_meta);
     m.impl("concat_volume", &concat_volume_meta);
     m.impl("corr_volume", &corr_volume_meta);
     m.impl("softargmin", &softargmin_meta);
