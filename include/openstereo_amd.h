@@ -35,6 +35,8 @@
  *   osa_*softargmin_var_f32     the three heads with disparity_variance beside the disparity,
  *                               models/cfnet/submodule.py:128-134, models/igevpp/submodule.py:153-159
  *   osa_mv2_block3d_f32         MobileStereoNet's 3-D inverted-residual block in eval mode, models/msnet/submodule.py:136-173
+ *   osa_interlaced_volume_f32   the interlaced cost volume of MSNet2D and of StereoBase's InterlacedVolume in eval mode,
+ *                               models/msnet/MSNet2D.py:143-162, stereo/modeling/cost_volume/cost_volume.py:120-169
  *   osa_geo_lookup_mr_*_f32     the multi-range lookup of IGEV++'s GRU loop (three geometry volumes of different disparity
  *                               ranges + the correlation pyramid -> four tensors), models/igevpp/geometry.py:6-87
  */
@@ -47,7 +49,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 12
+#define OSA_ABI_VERSION 13
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -677,6 +679,25 @@ int osa_mv2_block3d_pack_f32(const float* w_expand, const float* w_dw, const flo
                              int Ci, int Ch, int Co, void* stream);
 int osa_mv2_block3d_f32(const float* x, const float* packed, float* y, int B, int D, int H, int W, int Ci, int Ch, int Co, int stride, int residual,
                         void* stream);
+
+/* ---- The interlaced cost volume (models/msnet/MSNet2D.py:143-162; cost_volume.py:120-169, InterlacedVolume), ABI 13 ----
+ * Eval mode, ONE launch (csrc/interlaced_volume.hip).  Per plane i < min(D, W), on the crop of width W - i (left features from column i on,
+ * right features up to column W - i), the channels of the two maps are interwoven (left even, right odd) and reduced by three
+ * Conv3d + BN + ReLU whose depth stride equals their depth kernel (8, k2, k3) with widths 16, 32, 16, then a 1x1 Conv2d + BN + ReLU to F
+ * features; every layer pads its own input with zeros outside the crop.  featL, featR [B,C,H,W] and out [B,F,D,H,W] are fp32,
+ * contiguous; columns < i of plane i and planes >= W are written as zeros (out need not be initialised).  Exact fp32, no atomics, no
+ * workspace, bit-reproducible, independent of the batch size.  Supported: (C, k2, k3) = (32, 4, 2) (MSNet2D) and (96, 8, 3) (StereoBase),
+ * F in 1 .. 16, any B, H, W, D >= 1 with fewer than 2^31 elements in a feature map and in the volume.
+ * osa_interlaced_volume_pack_f32: the weights in the reference's layouts (w1 [16,1,8,3,3], w2 [32,16,k2,3,3], w3 [16,32,k3,3,3],
+ * w4 [F,16,1,1]) and the four folded BatchNorms (y = x * scale + shift per channel; a convolution's bias is folded into the shift:
+ * shift + scale * bias) -> `packed`, osa_interlaced_volume_packed_floats(C, k2, k3, F) floats (0 for unsupported arguments), in one
+ * small launch. */
+size_t osa_interlaced_volume_packed_floats(int C, int k2, int k3, int F);
+int osa_interlaced_volume_pack_f32(const float* w1, const float* w2, const float* w3, const float* w4, const float* scale1, const float* shift1,
+                                   const float* scale2, const float* shift2, const float* scale3, const float* shift3, const float* scale4,
+                                   const float* shift4, float* packed, int C, int k2, int k3, int F, void* stream);
+int osa_interlaced_volume_f32(const float* featL, const float* featR, const float* packed, float* out, int B, int C, int H, int W, int D, int k2, int k3,
+                              int F, void* stream);
 
 /* ---- input pre-processing on device ------------------------- */
 /* RightTopPad(edge) + HWC->CHW + /255 + (x-mean)/std for the left and right image in one launch

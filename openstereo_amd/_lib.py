@@ -155,6 +155,9 @@ SIGNATURES = {
     "osa_mv2_block3d_packed_floats": (C.c_size_t, [c_i] * 3),
     "osa_mv2_block3d_pack_f32": (c_i, [c_fp] * 10 + [c_i] * 3 + [c_st]),
     "osa_mv2_block3d_f32": (c_i, [c_fp] * 3 + [c_i] * 9 + [c_st]),
+    "osa_interlaced_volume_packed_floats": (C.c_size_t, [c_i] * 4),
+    "osa_interlaced_volume_pack_f32": (c_i, [c_fp] * 13 + [c_i] * 4 + [c_st]),
+    "osa_interlaced_volume_f32": (c_i, [c_fp] * 4 + [c_i] * 8 + [c_st]),
 }
 
 

@@ -202,6 +202,8 @@ def _graft(ref_cls, eng_cls, names, train_fallback=False):
             setattr(ref_cls, n, eng_cls.__dict__[n] if n in eng_cls.__dict__ else getattr(eng_cls, n))
     if train_fallback and orig_forward is not None and "forward" in names:
         eng_forward = eng_cls.__dict__["forward"]
+        _saved.append((ref_cls, "_ref_forward", _MISSING))
+        ref_cls._ref_forward = orig_forward                  # for mirrors that defer to it on their own conditions (msnet.MSNet2D)
 
         def forward(self, *a, **k):
             if self.training or _needs_grad(*a, *(p for p in self.parameters())):
@@ -241,6 +243,7 @@ def _graft_plan():
         (M + "igev.igev_stereo", {"hourglass": (IG.hourglass, ("forward", "forward_cl", "forward_train", "_unit_train", "_packed_layers", "reset_engine"), False)}),  # :51-76
         (M + "lightstereo.aggregation", {c: (getattr(LS, c), fwd, False) for c in ("Aggregation", "MobileV2Residual", "AttentionModule")}),
         (M + "msnet.submodule", {"MobileV2_Residual_3D": (MS.MobileV2Residual3D, ("forward", "reset_engine"), True)}),   # submodule.py:136-173: eval mode only
+        (M + "msnet.MSNet2D", {"MSNet2D": (MS.MSNet2D, ("forward", "reset_engine"), True)}),                   # MSNet2D.py:134-212: eval mode only
         (M + "igev.update", {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}),
         (M + "stereobase.gru_blocks", {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}),
     ]

@@ -180,6 +180,55 @@ at::Tensor mv2_block3d(const at::Tensor& x, const at::Tensor& packed, int64_t Ch
     return y;
 }
 
+// The interlaced cost volume of MSNet2D / StereoBase's InterlacedVolume in eval mode (csrc/interlaced_volume.hip).  Inference ops like mv2_block3d.
+struct IlvDims { int C, k2, k3, F; };
+static IlvDims ilv_pack_dims(const at::Tensor& w1, const at::Tensor& w2, const at::Tensor& w3, const at::Tensor& w4, at::TensorList bn) {
+    TORCH_CHECK(w1.dim() == 5 && w2.dim() == 5 && w3.dim() == 5 && w4.dim() == 4, "interlaced_volume_pack: weights must be three Conv3d weights and one Conv2d weight");
+    const int64_t k1 = w1.size(2), k2 = w2.size(2), k3 = w3.size(2), F = w4.size(0);
+    TORCH_CHECK(w1.sizes() == at::IntArrayRef({16, 1, k1, 3, 3}) && w2.sizes() == at::IntArrayRef({32, 16, k2, 3, 3}) && w3.sizes() == at::IntArrayRef({16, 32, k3, 3, 3}) &&
+                w4.sizes() == at::IntArrayRef({F, 16, 1, 1}), "interlaced_volume_pack: weights must be [16,1,k1,3,3], [32,16,k2,3,3], [16,32,k3,3,3] and [F,16,1,1]");
+    TORCH_CHECK(k1 == 8 && osa_interlaced_volume_packed_floats((int)(k1 * k2 * k3 / 2), (int)k2, (int)k3, (int)F) > 0, "interlaced_volume_pack: depth kernels (", k1, ", ", k2, ", ", k3,
+                ") with ", F, " features (supported: (8, 4, 2) and (8, 8, 3), 1 .. 16 features)");
+    const int64_t n[8] = {16, 16, 32, 32, 16, 16, F, F};
+    for (int i = 0; i < 8; ++i)
+        TORCH_CHECK(bn[i].dim() == 1 && bn[i].size(0) == n[i], "interlaced_volume_pack: folded BatchNorm vector ", i, " has shape ", bn[i].sizes(), ", expected [", n[i], "]");
+    return {(int)(k1 * k2 * k3 / 2), (int)k2, (int)k3, (int)F};
+}
+at::Tensor interlaced_volume_pack_meta(const at::Tensor& w1, const at::Tensor& w2, const at::Tensor& w3, const at::Tensor& w4, const at::Tensor& s1, const at::Tensor& t1,
+                                       const at::Tensor& s2, const at::Tensor& t2, const at::Tensor& s3, const at::Tensor& t3, const at::Tensor& s4, const at::Tensor& t4) {
+    const IlvDims d = ilv_pack_dims(w1, w2, w3, w4, {s1, t1, s2, t2, s3, t3, s4, t4});
+    return at::empty({(int64_t)osa_interlaced_volume_packed_floats(d.C, d.k2, d.k3, d.F)}, w1.options().dtype(at::kFloat));
+}
+at::Tensor interlaced_volume_pack(const at::Tensor& w1, const at::Tensor& w2, const at::Tensor& w3, const at::Tensor& w4, const at::Tensor& s1, const at::Tensor& t1,
+                                  const at::Tensor& s2, const at::Tensor& t2, const at::Tensor& s3, const at::Tensor& t3, const at::Tensor& s4, const at::Tensor& t4) {
+    at::Tensor t[12];
+    int i = 0;
+    for (const at::Tensor* s : {&w1, &w2, &w3, &w4, &s1, &t1, &s2, &t2, &s3, &t3, &s4, &t4}) t[i++] = gpu_f32(*s, "interlaced_volume_pack argument").detach().contiguous();
+    const IlvDims d = ilv_pack_dims(w1, w2, w3, w4, {s1, t1, s2, t2, s3, t3, s4, t4});
+    auto packed = interlaced_volume_pack_meta(w1, w2, w3, w4, s1, t1, s2, t2, s3, t3, s4, t4);
+    OSA_CALL(osa_interlaced_volume_pack_f32(fp(t[0]), fp(t[1]), fp(t[2]), fp(t[3]), fp(t[4]), fp(t[5]), fp(t[6]), fp(t[7]), fp(t[8]), fp(t[9]), fp(t[10]), fp(t[11]),
+                                            packed.data_ptr<float>(), d.C, d.k2, d.k3, d.F, cur_stream()));
+    return packed;
+}
+// -> [B, F, maxdisp, H, W], contiguous
+at::Tensor interlaced_volume_meta(const at::Tensor& left, const at::Tensor& right, const at::Tensor& packed, int64_t maxdisp, int64_t k2, int64_t k3, int64_t F) {
+    TORCH_CHECK(left.dim() == 4 && left.sizes() == right.sizes(), "interlaced_volume: features must be [B,C,H,W] of equal shape");
+    TORCH_CHECK(maxdisp > 0, "interlaced_volume: maxdisp ", maxdisp);
+    const size_t n = osa_interlaced_volume_packed_floats((int)left.size(1), (int)k2, (int)k3, (int)F);
+    TORCH_CHECK(n > 0, "interlaced_volume: ", left.size(1), " channels with depth kernels (8, ", k2, ", ", k3, ") and ", F,
+                " features (supported: 32 channels with (8, 4, 2), 96 with (8, 8, 3), 1 .. 16 features)");
+    TORCH_CHECK(packed.dim() == 1 && packed.size(0) == (int64_t)n, "interlaced_volume: packed parameters of ", packed.numel(), " floats do not belong to this configuration (", n, ")");
+    return at::empty({left.size(0), F, maxdisp, left.size(2), left.size(3)}, left.options().dtype(at::kFloat));
+}
+at::Tensor interlaced_volume(const at::Tensor& left, const at::Tensor& right, const at::Tensor& packed, int64_t maxdisp, int64_t k2, int64_t k3, int64_t F) {
+    gpu_f32(left, "left"); gpu_f32(right, "right"); gpu_f32(packed, "packed");
+    auto out = interlaced_volume_meta(left, right, packed, maxdisp, k2, k3, F);
+    const auto l = left.contiguous(), r = right.contiguous();
+    OSA_CALL(osa_interlaced_volume_f32(fp(l), fp(r), fp(packed), out.data_ptr<float>(), (int)l.size(0), (int)l.size(1), (int)l.size(2), (int)l.size(3), (int)maxdisp, (int)k2, (int)k3,
+                                       (int)F, cur_stream()));
+    return out;
+}
+
 // ---- regression heads ----------------------------------------------------------------------------------------------------------
 at::Tensor softargmin(const at::Tensor& prob) {
     gpu_f32(prob, "prob");
@@ -1276,6 +1325,8 @@ TORCH_LIBRARY(osa_native, m) {
     m.def("mr_volume(Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last=False) -> (Tensor, Tensor, Tensor)");
     m.def("mv2_block3d_pack(Tensor w_expand, Tensor w_dw, Tensor w_project, Tensor scale1, Tensor shift1, Tensor scale2, Tensor shift2, Tensor scale3, Tensor shift3) -> Tensor");
     m.def("mv2_block3d(Tensor x, Tensor packed, int hidden, int out_channels, int stride, bool residual) -> Tensor");
+    m.def("interlaced_volume_pack(Tensor w1, Tensor w2, Tensor w3, Tensor w4, Tensor scale1, Tensor shift1, Tensor scale2, Tensor shift2, Tensor scale3, Tensor shift3, Tensor scale4, Tensor shift4) -> Tensor");
+    m.def("interlaced_volume(Tensor left, Tensor right, Tensor packed, int maxdisp, int k2, int k3, int features) -> Tensor");
     m.def("mr_volume_bwd(Tensor? dv0, Tensor? dv1, Tensor? dv2, Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("concat_volume(Tensor left, Tensor right, int maxdisp, bool mask_left=True) -> Tensor");
     m.def("corr_volume(Tensor left, Tensor right, int maxdisp) -> Tensor");
@@ -1349,6 +1400,8 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
     m.impl("mr_volume_bwd", &mr_volume_bwd);
     m.impl("mv2_block3d_pack", &mv2_block3d_pack);
     m.impl("mv2_block3d", &mv2_block3d);
+    m.impl("interlaced_volume_pack", &interlaced_volume_pack);
+    m.impl("interlaced_volume", &interlaced_volume);
     m.impl("concat_volume", &concat_volume);
     m.impl("corr_volume", &corr_volume);
     m.impl("softargmin", &softargmin);
@@ -1414,6 +1467,8 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
     m.impl("mr_volume_bwd", &mr_volume_bwd_meta);
     m.impl("mv2_block3d_pack", &mv2_block3d_pack_meta);
     m.impl("mv2_block3d", &mv2_block3d_meta);
+    m.impl("interlaced_volume_pack", &interlaced_volume_pack_meta);
+    m.impl("interlaced_volume", &interlaced_volume_meta);
     m.impl("concat_volume", &concat_volume_meta);
     m.impl("corr_volume", &corr_volume_meta);
     m.impl("softargmin", &softargmin_meta);

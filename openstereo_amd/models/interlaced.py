@@ -13,17 +13,34 @@ outermost in the channel index (kd * Cin + c) the regrouping between stages is a
     [B,192,H,W'] = [B*24, 8, H, W']      --conv2d   8 -> 16-->  [B*24, 16, H, W'] = [B*3, 8*16, H, W']
                                           --conv2d 128 -> 32-->  [B*3, 32, H, W']  = [B, 3*32, H, W']
                                           --conv2d  96 -> 16-->  [B, 16, H, W']  --1x1 16 -> F-->  [B, F, H, W']
-In eval mode on the GPU these four layers are fused conv + BN + ReLU launches of the engine's 2-D MFMA kernels, per disparity on the
-cropped width (the crop's zero padding is part of the semantics: column x = i sees zeros at x = i - 1, not the neighbouring pixel).
+In eval mode on the GPU the whole volume is ONE launch (csrc/interlaced_volume.hip): a workgroup owns a tile of one plane,
+streams along depth with one A1 and one A2 group resident in LDS, and the crop and the interweave are address arithmetic (the crop's zero
+padding is part of the semantics: column x = i sees zeros at x = i - 1, not the neighbouring pixel).
 In training mode the module is the reference's torch composition."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from ..engine import PackedConv3d, cached_pack, ACT_RELU
-from ..ops import to_cl, to_ncdhw, on_engine
+from .. import _ext
+from ..engine import bn_scale_shift, cached_pack
+from ..ops import on_engine
 from .igev_style import BasicConv2d, BasicConv3d
+
+
+def interlaced_volume(owner, convs, bns, feat_l, feat_r, maxdisp):
+    """Three depth-strided Conv3d and a 1x1 Conv2d with their BatchNorms -> [B,F,maxdisp,H,W]: one cached pack (a conv bias is folded into
+    the BN shift) and one launch."""
+    ns = _ext.load()
+
+    def pack():
+        st = []
+        for c, bn in zip(convs, bns):
+            s, t = bn_scale_shift(bn)
+            st += [s, t if c.bias is None else t + s * c.bias.detach().float()]
+        return ns.interlaced_volume_pack(*(c.weight for c in convs), *st)
+    pk = cached_pack(owner, "_eng", pack, mods=list(convs) + list(bns))
+    return ns.interlaced_volume(feat_l.float(), feat_r.float(), pk, maxdisp, convs[1].kernel_size[0], convs[2].kernel_size[0], convs[3].out_channels)
 
 
 class InterlacedVolume(nn.Module):
@@ -42,16 +59,6 @@ class InterlacedVolume(nn.Module):
     def interweave_tensors(refimg_fea, targetimg_fea):
         B, C, H, W = refimg_fea.shape
         return torch.stack((refimg_fea, targetimg_fea), 2).reshape(B, 2 * C, H, W)       # left at even, right at odd channels
-
-    def _packs(self):
-        def flat(block):
-            """Conv3d whose depth stride equals its depth kernel -> the 2-D layer over kd * Cin channels (depth tap outermost)."""
-            conv, bn = block.block[0], block.block[1]
-            Co, Ci, kd = conv.weight.shape[:3]
-            c2 = nn.Conv2d(Ci * kd, Co, 3, padding=1, bias=False).to(conv.weight.device)
-            c2.weight.data = conv.weight.detach().permute(0, 2, 1, 3, 4).reshape(Co, kd * Ci, 3, 3).contiguous()
-            return PackedConv3d(c2, bn, ACT_RELU)
-        return [flat(b) for b in self.conv3d] + [PackedConv3d(self.volume11.block[0], self.volume11.block[1], ACT_RELU)]
 
     def _forward_torch(self, feat_l, feat_r, maxdisp):
         B, C, H, W = feat_l.shape
@@ -73,17 +80,5 @@ class InterlacedVolume(nn.Module):
             return self._forward_torch(feat_l, feat_r, maxdisp)
         if not on_engine(feat_l):
             raise RuntimeError("openstereo_amd InterlacedVolume runs on the GPU engine only (no CPU path)")
-        e = cached_pack(self, "_eng", self._packs)
-        fl, fr = feat_l.float(), feat_r.float()
-        volume = fl.new_zeros([B, self.num_features, maxdisp, H, W])
-        for i in range(min(maxdisp, W)):
-            Wc = W - i
-            x = self.interweave_tensors(fl[:, :, :, i:], fr[:, :, :, :Wc])                     # [B,192,H,Wc]
-            x = to_cl(x.reshape(B * 24, 8, 1, H, Wc))
-            x = e[0](x)                                                                          # [B*24,16,1,H,Wc] NHWC
-            x = to_cl(to_ncdhw(x, 16).reshape(B * 3, 128, 1, H, Wc))                            # depth groups of 8 -> channels kd * 16 + c
-            x = e[1](x)
-            x = to_cl(to_ncdhw(x, 32).reshape(B, 96, 1, H, Wc))
-            x = e[3](e[2](x))
-            volume[:, :, i, :, i:] = to_ncdhw(x, self.num_features)[:, :, 0]
-        return volume
+        blk = [b.block for b in self.conv3d] + [self.volume11.block]
+        return interlaced_volume(self, [b[0] for b in blk], [b[1] for b in blk], feat_l, feat_r, maxdisp)
