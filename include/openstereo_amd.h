@@ -35,6 +35,8 @@
  *   osa_*softargmin_var_f32     the three heads with disparity_variance beside the disparity,
  *                               models/cfnet/submodule.py:128-134, models/igevpp/submodule.py:153-159
  *   osa_mv2_block3d_f32         MobileStereoNet's 3-D inverted-residual block in eval mode, models/msnet/submodule.py:136-173
+ *   osa_mv2_block2d_f32         MobileStereoNet's 2-D inverted-residual block in eval mode with the caller's addend and ReLU,
+ *                               models/msnet/submodule.py:94-133, models/msnet/MSNet2D.py:10-45
  *   osa_interlaced_volume_f32   the interlaced cost volume of MSNet2D and of StereoBase's InterlacedVolume in eval mode,
  *                               models/msnet/MSNet2D.py:143-162, stereo/modeling/cost_volume/cost_volume.py:120-169
  *   osa_geo_lookup_mr_*_f32     the multi-range lookup of IGEV++'s GRU loop (three geometry volumes of different disparity
@@ -49,7 +51,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 13
+#define OSA_ABI_VERSION 14
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -679,6 +681,25 @@ int osa_mv2_block3d_pack_f32(const float* w_expand, const float* w_dw, const flo
                              int Ci, int Ch, int Co, void* stream);
 int osa_mv2_block3d_f32(const float* x, const float* packed, float* y, int B, int D, int H, int W, int Ci, int Ch, int Co, int stride, int residual,
                         void* stream);
+
+/* ---- MobileStereoNet's 2-D inverted-residual block (models/msnet/submodule.py:94-133, MobileV2_Residual), ABI 14 ----
+ * Eval mode, ONE launch (csrc/mv2_block2d.hip):  y = bn3(W3 relu6(bn2(dw3x3(relu6(bn1(W1 x)))))), then y = x + y when residual, then
+ * y = y + addend when addend is not NULL (same shape as y), then y = relu(y) when relu: the sums and the ReLU with which MSNet2D's
+ * hourglass2D and dres stages follow a block (MSNet2D.py:42-43, 86-93).  A 1x1 expansion Ci -> Ch, a depthwise 3x3 convolution of
+ * stride 1 or 2, padding 1 and dilation 1 (zeros around the HIDDEN tensor) and a 1x1 projection Ch -> Co.  x [B,H,W,Ci], y and addend
+ * [B,Ho,Wo,Co] are fp32 NHWC, Ho = (H - 1) / stride + 1 and likewise Wo; y must not overlap x or addend; the hidden tensors never reach
+ * memory.  Exact fp32 in every arithmetic mode, no atomics, bit-reproducible, independent of the batch size.
+ * Supported: Ci, Ch, Co multiples of 8, Ci and Co <= 192, Ch <= 384, stride 1 or 2, any B, H, W >= 1 with fewer than 2^31 elements in x
+ * and in y; residual needs stride 1 and Ci == Co.  Every error is reported before anything is launched.
+ * osa_mv2_block2d_pack_f32: the three weights in the reference's layouts (w_expand [Ch,Ci,1,1], w_dw [Ch,1,3,3], w_project [Co,Ch,1,1])
+ * and the three folded BatchNorms (y = x * scale + shift, per channel) -> `packed`, osa_mv2_block2d_packed_floats(Ci, Ch, Co) =
+ * Ch (Ci + Co + 13) + 2 Co floats (0 for non-positive arguments), in one small launch. */
+size_t osa_mv2_block2d_packed_floats(int Ci, int Ch, int Co);
+int osa_mv2_block2d_pack_f32(const float* w_expand, const float* w_dw, const float* w_project, const float* scale1, const float* shift1,
+                             const float* scale2, const float* shift2, const float* scale3, const float* shift3, float* packed,
+                             int Ci, int Ch, int Co, void* stream);
+int osa_mv2_block2d_f32(const float* x, const float* packed, const float* addend, float* y, int B, int H, int W, int Ci, int Ch, int Co, int stride,
+                        int residual, int relu, void* stream);
 
 /* ---- The interlaced cost volume (models/msnet/MSNet2D.py:143-162; cost_volume.py:120-169, InterlacedVolume), ABI 13 ----
  * Eval mode, ONE launch (csrc/interlaced_volume.hip).  Per plane i < min(D, W), on the crop of width W - i (left features from column i on,

@@ -39,53 +39,43 @@ class NhwcRef(C.Structure):
 
 c_ref = C.POINTER(NhwcRef)
 
-# name -> (restype, argtypes).  Mirrors include/openstereo_amd.h one to one; tests check that
+# name -> (restype, argtypes).  Mirrors include/openstereo_amd.h; entry points with one prototype share a line; tests check that
 # every symbol declared in the header is listed here and exported by the .so.
 _LEVELS = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(c_i), C.POINTER(c_i), c_i]   # geo / corr pointer and length arrays (host), levels
 SIGNATURES = {
     "osa_abi_version": (c_i, []),
-    "osa_last_error": (C.c_char_p, []),
-    "osa_target_arch": (C.c_char_p, []),
+    **dict.fromkeys(("osa_last_error", "osa_target_arch"), (C.c_char_p, [])),
     "osa_build_volume_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_fp, c_fp, c_i, c_fp] + [c_i] * 8 + [c_fp, c_st]),
     "osa_build_volume_nhwc_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp] + [c_i] * 7 + [c_fp, c_st]),
-    "osa_corr_volume_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_ncdhw_to_ndhwc_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_ll, c_i, c_i, c_st]),
-    "osa_ndhwc_to_ncdhw_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_ll, c_i, c_i, c_st]),
-    "osa_conv3d_packed_floats": (C.c_size_t, [c_i, c_i, c_i, c_i, c_i]),
-    "osa_conv3d_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_deconv3d_packed_floats": (C.c_size_t, [c_i, c_i, c_i]),
-    "osa_deconv3d_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_conv3d_ndhwc_f32": (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_st]),
-    "osa_deconv3d_ndhwc_f32": (c_i, [c_fp] * 6 + [c_i] * 12 + [c_fp, c_i, c_i, c_f, c_st]),
+    **dict.fromkeys(("osa_corr_volume_f32", "osa_allpairs_corr_f32"), (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st])),
+    **dict.fromkeys(("osa_ncdhw_to_ndhwc_f32", "osa_ndhwc_to_ncdhw_f32"), (c_i, [c_fp, c_fp, c_i, c_i, c_ll, c_i, c_i, c_st])),
+    **dict.fromkeys(("osa_conv3d_packed_floats", "osa_conv3d_small_co_packed_floats"), (C.c_size_t, [c_i, c_i, c_i, c_i, c_i])),
+    **dict.fromkeys(("osa_conv3d_pack_f32", "osa_conv3d_small_co_pack_f32", "osa_conv3d_pack_f16"), (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st])),
+    **dict.fromkeys(("osa_deconv3d_packed_floats", "osa_deconv2d_packed_floats"), (C.c_size_t, [c_i, c_i, c_i])),
+    **dict.fromkeys(("osa_deconv3d_pack_f32", "osa_softargmin_bwd_f32", "osa_deconv2d_pack_f32", "osa_deconv3d_pack_f16", "osa_deconv2d_pack_f16", "osa_softargmin_f32"), (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st])),
+    **dict.fromkeys(("osa_conv3d_ndhwc_f32", "osa_conv3d_ndhwc_f16"), (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_st])),
+    **dict.fromkeys(("osa_deconv3d_ndhwc_f32", "osa_deconv3d_ndhwc_f16"), (c_i, [c_fp] * 6 + [c_i] * 12 + [c_fp, c_i, c_i, c_f, c_st])),
     "osa_conv3d_pack_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_st]),
-    "osa_deconv3d_pack_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_st]),
+    **dict.fromkeys(("osa_deconv3d_pack_f16x3", "osa_deconv2d_pack_f16x3"), (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_st])),
     "osa_conv3d_ndhwc_f16x3": (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_f, c_rng, c_st]),
     "osa_deconv3d_ndhwc_f16x3": (c_i, [c_fp] * 6 + [c_i] * 12 + [c_fp, c_i, c_i, c_f, c_f, c_rng, c_st]),
     "osa_conv3d_pack_ex": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_st]),
     "osa_pair_volume_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_conv3d_wgrad_f32": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 22 + [c_st]),
-    "osa_conv3d_wgrad_workspace_bytes": (C.c_size_t, [c_i] * 20),
+    **dict.fromkeys(("osa_conv3d_wgrad_workspace_bytes", "osa_conv3d_wgrad_f16x3_workspace_bytes"), (C.c_size_t, [c_i] * 20)),
     "osa_conv3d_wgrad_ws_f32": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 22 + [c_fp, C.c_size_t, c_st]),
-    "osa_conv3d_wgrad_f16x3_workspace_bytes": (C.c_size_t, [c_i] * 20),
     "osa_conv3d_wgrad_ws_f16x3": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 22 + [c_fp, c_fp, c_fp, C.c_size_t, c_st]),
     "osa_conv3d_wgrad_ws_f16": (c_i, [c_fp, c_fp, c_fp] + [c_i] * 22 + [c_fp, c_fp, c_i, c_i, c_fp, C.c_size_t, c_st]),
-    "osa_conv3d_small_co_ndhwc_f32": (c_i, [c_fp] * 5 + [c_i] * 14 + [c_st]),
-    "osa_conv3d_small_co_packed_floats": (C.c_size_t, [c_i, c_i, c_i, c_i, c_i]),
-    "osa_conv3d_small_co_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_conv3d_small_co_packed_ndhwc_f32": (c_i, [c_fp] * 5 + [c_i] * 14 + [c_st]),
+    **dict.fromkeys(("osa_conv3d_small_co_ndhwc_f32", "osa_conv3d_small_co_packed_ndhwc_f32"), (c_i, [c_fp] * 5 + [c_i] * 14 + [c_st])),
     "osa_build_volume_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_softargmin_bwd_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_softmax_softargmin_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_upsample_softargmin_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    **dict.fromkeys(("osa_softmax_softargmin_bwd_f32", "osa_softmax_softargmin_f32", "osa_softmax_softargmin_var_f32"), (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st])),
+    **dict.fromkeys(("osa_upsample_softargmin_bwd_f32", "osa_upsample_softargmin_var_f32"), (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st])),
     "osa_amax_f32": (c_i, [c_fp, C.c_longlong, c_fp, c_st]),
-    "osa_upsample_softargmin_bwd_workspace_bytes": (C.c_size_t, [c_i] * 4),
+    **dict.fromkeys(("osa_upsample_softargmin_bwd_workspace_bytes", "osa_mr_volume_bwd_workspace_bytes", "osa_interlaced_volume_packed_floats"), (C.c_size_t, [c_i] * 4)),
     "osa_upsample_softargmin_bwd_ws_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, C.c_size_t, c_st]),
     "osa_deconv3d_redir_ndhwc_f32": (c_i, [c_fp] * 5 + [c_i] * 11 + [c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_f, c_st]),
     "osa_deconv3d_redir_ndhwc_f16x3": (c_i, [c_fp] * 5 + [c_i] * 11 + [c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_f, c_i, c_f, c_f, c_rng, c_st]),
-    "osa_deconv2d_packed_floats": (C.c_size_t, [c_i, c_i, c_i]),
-    "osa_deconv2d_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_deconv2d_pack_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_st]),
-    "osa_deconv2d_nhwc_f32": (c_i, [c_fp] * 6 + [c_i] * 11 + [c_fp, c_i, c_i, c_f, c_st]),
+    **dict.fromkeys(("osa_deconv2d_nhwc_f32", "osa_deconv2d_nhwc_f16"), (c_i, [c_fp] * 6 + [c_i] * 11 + [c_fp, c_i, c_i, c_f, c_st])),
     "osa_deconv2d_nhwc_f16x3": (c_i, [c_fp] * 6 + [c_i] * 11 + [c_fp, c_i, c_i, c_f, c_f, c_rng, c_st]),
     "osa_dwconv2d_pack_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_st]),
     "osa_dwconv2d_nhwc_f32": (c_i, [c_fp] * 6 + [c_i] * 15 + [c_fp, c_st]),
@@ -97,31 +87,20 @@ SIGNATURES = {
     "osa_gru_gates_q_bwd": (c_i, [c_ref, c_ref, c_fp, c_ref, c_ref, c_ref, c_ref, c_ref, c_ref, c_ll, c_i, c_st]),
     "osa_disp_update_f32": (c_i, [c_fp, c_fp, c_i, c_fp, c_fp, c_i, c_ll, c_fp, c_fp, c_st]),
     "osa_conv3d_pack_ex_auto": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_st]),
-    "osa_deconv3d_pack_f16x3_auto": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_st]),
-    "osa_deconv2d_pack_f16x3_auto": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_st]),
+    **dict.fromkeys(("osa_deconv3d_pack_f16x3_auto", "osa_deconv2d_pack_f16x3_auto"), (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_fp, c_fp, c_st])),
     "osa_cat_fms_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_pool2x_nhwc_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_st]),
     "osa_resize_bilinear_nhwc_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, c_fp, c_st]),
     "osa_context_upsample_logits_f32": (c_i, [c_fp, c_fp, c_i, C.POINTER(c_ll), c_fp, c_i, c_i, c_i, c_i, c_f, c_st]),
     "osa_context_upsample_logits_bwd_f32": (c_i, [c_fp, c_fp, c_i, C.POINTER(c_ll), c_fp, c_fp, c_fp, C.POINTER(c_ll), c_fp, c_i, c_i, c_i, c_i, c_f, c_st]),
     "osa_context_upsample_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_st]),
-    "osa_allpairs_corr_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_geo_rows_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_avgpool_rows_f32": (c_i, [c_fp, c_fp, c_ll, c_i, c_st]),
-    "osa_geo_lookup_f32": (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
+    **dict.fromkeys(("osa_geo_lookup_f32", "osa_geo_lookup_bwd_acc_f32", "osa_geo_lookup_bwd_f32"), (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st])),
     "osa_geo_lookup_nhwc_f32": (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_geo_lookup_bwd_acc_f32": (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_geo_lookup_bwd_f32": (c_i, _LEVELS + [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_geo_lookup_mr_f32": (c_i, _LEVELS + [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
+    **dict.fromkeys(("osa_geo_lookup_mr_f32", "osa_geo_lookup_mr_bwd_acc_f32"), (c_i, _LEVELS + [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st])),
     "osa_geo_lookup_mr_nhwc_f32": (c_i, _LEVELS + [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_geo_lookup_mr_bwd_acc_f32": (c_i, _LEVELS + [c_fp, c_i, c_fp, c_i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
     "osa_preprocess_pair_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_f), C.POINTER(c_f), c_fp, c_i, c_st]),
-    "osa_conv3d_pack_f16": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_deconv3d_pack_f16": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_deconv2d_pack_f16": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_conv3d_ndhwc_f16": (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_st]),
-    "osa_deconv3d_ndhwc_f16": (c_i, [c_fp] * 6 + [c_i] * 12 + [c_fp, c_i, c_i, c_f, c_st]),
-    "osa_deconv2d_nhwc_f16": (c_i, [c_fp] * 6 + [c_i] * 11 + [c_fp, c_i, c_i, c_f, c_st]),
     "osa_instnorm_workspace_floats": (C.c_size_t, [c_i, c_ll, c_i]),
     "osa_instnorm_nhwc_f32": (c_i, [c_fp, c_fp, c_i, c_ll, c_i, c_i, c_i, c_f, c_i, c_f, c_fp, c_fp, c_st]),
     "osa_conv3d_wgrad_ws_multi": (c_i, [c_i, c_fp, c_fp, c_i, c_fp] + [c_i] * 22 + [c_fp, c_fp, c_i, c_i, c_fp, C.c_size_t, c_st]),
@@ -129,33 +108,20 @@ SIGNATURES = {
     "osa_channel_affine": (c_i, [c_fp, c_i, c_i, c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_fp, c_i, c_ll, c_i, c_i, c_st]),
     "osa_channel_sums_multi": (c_i, [c_fp, c_i, c_i, c_i, c_ll, c_i, c_fp, c_fp, C.c_size_t, c_st]),
     "osa_channel_sums": (c_i, [c_fp, c_i, c_i, c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_ll, c_i, c_fp, c_fp, C.c_size_t, c_st]),
-    "osa_conv3d_march_launches": (c_ll, []),
-    "osa_conv3d_march_s2_launches": (c_ll, []),
-    "osa_deconv_walk": (c_i, [c_i]),
-    "osa_deconv_walk_segment_planes": (c_i, [c_i]),
-    "osa_deconv3d_walk_launches": (c_ll, []),
-    "osa_conv_b_ring_mask": (c_i, [c_i]),
-    "osa_conv_b_ring_launches": (c_ll, []),
-    "osa_volume_walk_step": (c_i, [c_i]),
-    "osa_volume_walk_launches": (c_ll, []),
+    **dict.fromkeys(("osa_conv3d_march_launches", "osa_conv3d_march_s2_launches", "osa_deconv3d_walk_launches", "osa_conv_b_ring_launches", "osa_volume_walk_launches"), (c_ll, [])),
+    **dict.fromkeys(("osa_deconv_walk", "osa_deconv_walk_segment_planes", "osa_conv_b_ring_mask", "osa_volume_walk_step"), (c_i, [c_i])),
     "osa_build_volume_nhwc_split_eligible": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
     "osa_build_volume_nhwc_split_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp] + [c_i] * 7 + [c_fp, c_fp, c_fp, c_st]),
-    "osa_softargmin_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_softmax_softargmin_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_upsample_softargmin_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
-    "osa_softargmin_var_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_softmax_softargmin_var_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_upsample_softargmin_var_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),
+    **dict.fromkeys(("osa_softargmin_var_f32", "osa_softmax_softargmin_var_bwd_f32"), (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st])),
     "osa_softargmin_var_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
-    "osa_softmax_softargmin_var_bwd_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st]),
     "osa_upsample_softargmin_var_bwd_ws_f32": (c_i, [c_fp, c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, C.c_size_t, c_st]),
     "osa_mr_volume_f32": (c_i, [c_fp] * 7 + [c_i] * 12 + [c_st]),
-    "osa_mr_volume_bwd_workspace_bytes": (C.c_size_t, [c_i] * 4),
     "osa_mr_volume_bwd_ws_f32": (c_i, [c_fp] * 3 + [c_i] + [c_fp] * 8 + [c_i] * 11 + [c_fp, C.c_size_t, c_st]),
-    "osa_mv2_block3d_packed_floats": (C.c_size_t, [c_i] * 3),
-    "osa_mv2_block3d_pack_f32": (c_i, [c_fp] * 10 + [c_i] * 3 + [c_st]),
+    **dict.fromkeys(("osa_mv2_block3d_packed_floats", "osa_mv2_block2d_packed_floats"), (C.c_size_t, [c_i] * 3)),
+    **dict.fromkeys(("osa_mv2_block3d_pack_f32", "osa_mv2_block2d_pack_f32"), (c_i, [c_fp] * 10 + [c_i] * 3 + [c_st])),
     "osa_mv2_block3d_f32": (c_i, [c_fp] * 3 + [c_i] * 9 + [c_st]),
-    "osa_interlaced_volume_packed_floats": (C.c_size_t, [c_i] * 4),
+    "osa_mv2_block2d_f32": (c_i, [c_fp] * 4 + [c_i] * 9 + [c_st]),
     "osa_interlaced_volume_pack_f32": (c_i, [c_fp] * 13 + [c_i] * 4 + [c_st]),
     "osa_interlaced_volume_f32": (c_i, [c_fp] * 4 + [c_i] * 8 + [c_st]),
 }
@@ -174,9 +140,7 @@ def load():
         if _lib is not None:
             return _lib
         if not os.path.exists(LIB_PATH):
-            raise EngineError(
-                f"{LIB_PATH} is missing: build it with `python -m openstereo_amd.build` "
-                "(hipcc, gfx950). There is no CPU fallback.")
+            raise EngineError(f"{LIB_PATH} is missing: build it with `python -m openstereo_amd.build` (hipcc, gfx950). There is no CPU fallback.")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)       # AttributeError if the .so does not export it

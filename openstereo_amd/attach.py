@@ -242,7 +242,8 @@ def _graft_plan():
         (M + "igev.submodule", {"FeatureAtt": (IG.IGEVFeatureAtt, ("logits",), False)}),
         (M + "igev.igev_stereo", {"hourglass": (IG.hourglass, ("forward", "forward_cl", "forward_train", "_unit_train", "_packed_layers", "reset_engine"), False)}),  # :51-76
         (M + "lightstereo.aggregation", {c: (getattr(LS, c), fwd, False) for c in ("Aggregation", "MobileV2Residual", "AttentionModule")}),
-        (M + "msnet.submodule", {"MobileV2_Residual_3D": (MS.MobileV2Residual3D, ("forward", "reset_engine"), True)}),   # submodule.py:136-173: eval mode only
+        (M + "msnet.submodule", {"MobileV2_Residual_3D": (MS.MobileV2Residual3D, ("forward", "reset_engine"), True),     # submodule.py:136-173: eval mode only
+                                 "MobileV2_Residual": (MS.MobileV2Residual2D, ("forward", "reset_engine"), True)}),       # submodule.py:94-133: eval mode only
         (M + "msnet.MSNet2D", {"MSNet2D": (MS.MSNet2D, ("forward", "reset_engine"), True)}),                   # MSNet2D.py:134-212: eval mode only
         (M + "igev.update", {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}),
         (M + "stereobase.gru_blocks", {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}),

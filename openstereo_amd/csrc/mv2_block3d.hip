@@ -25,14 +25,13 @@
 //
 // Packed parameters (osa_mv2_block3d_pack_f32), Ch (Ci + Co + 31) + 2 Co floats:
 //   W1 [Ch][Ci] | s1 [Ch] | b1 [Ch] | DW [27][Ch] | s2 [Ch] | b2 [Ch] | W3 [Co][Ch] | s3 [Co] | b3 [Co]
-#include "osa_common.h"
+#include "mv2_common.h"
 #include <algorithm>
 
 namespace osa {
 
 constexpr int MV2_NT = 512, MV2_MAX_CIO = 128, MV2_MAX_CH = 256;
 typedef float mv2_f32x16 __attribute__((ext_vector_type(16)));
-typedef float mv2_f32x4 __attribute__((ext_vector_type(4)));
 
 struct Mv2Args {
     const float* x; const float* pk; float* y;
@@ -40,10 +39,6 @@ struct Mv2Args {
     int nTx, nTy, DCH, nCh;                  // tiles along w / h, output planes per workgroup, chunks of planes
 };
 
-static inline size_t mv2_packed_floats(int Ci, int Ch, int Co) { return (size_t)Ch * (Ci + Co + 31) + 2 * (size_t)Co; }
-
-__device__ __forceinline__ float relu6f(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ mv2_f32x16 mfma8(const float4 a, const float4 b, mv2_f32x16 c) {
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, c, 0, 0, 0);
@@ -205,35 +200,6 @@ __global__ __launch_bounds__(MV2_NT) void mv2_block3d_kernel(const Mv2Args p) {
     }
 }
 
-// W1 [Ch,Ci] | s1 | b1 | DW [Ch,27] -> [27][Ch] | s2 | b2 | W3 [Co,Ch] | s3 | b3
-__global__ __launch_bounds__(256) void mv2_block3d_pack_kernel(const float* __restrict__ w1, const float* __restrict__ wd, const float* __restrict__ w3,
-                                                                const float* __restrict__ s1, const float* __restrict__ b1, const float* __restrict__ s2,
-                                                                const float* __restrict__ b2, const float* __restrict__ s3, const float* __restrict__ b3,
-                                                                float* __restrict__ pk, int Ci, int Ch, int Co) {
-    const int n1 = Ch * Ci, n3 = Co * Ch, total = n1 + 31 * Ch + n3 + 2 * Co;
-    int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    float v;
-    if (i < n1) v = w1[i];
-    else if ((i -= n1) < Ch) v = s1[i];
-    else if ((i -= Ch) < Ch) v = b1[i];
-    else if ((i -= Ch) < 27 * Ch) v = wd[(i % Ch) * 27 + i / Ch];
-    else if ((i -= 27 * Ch) < Ch) v = s2[i];
-    else if ((i -= Ch) < Ch) v = b2[i];
-    else if ((i -= Ch) < n3) v = w3[i];
-    else if ((i -= n3) < Co) v = s3[i];
-    else v = b3[i - Co];
-    pk[blockIdx.x * 256 + threadIdx.x] = v;
-}
-
-static int mv2_check_channels(const char* who, int Ci, int Ch, int Co) {
-    OSA_REQUIRE(Ci > 0 && Ch > 0 && Co > 0, "%s: bad dims", who);
-    OSA_REQUIRE(Ci % 8 == 0 && Ch % 8 == 0 && Co % 8 == 0, "%s: channels %d -> %d -> %d (supported: multiples of 8)", who, Ci, Ch, Co);
-    OSA_REQUIRE(Ci <= MV2_MAX_CIO && Co <= MV2_MAX_CIO && Ch <= MV2_MAX_CH, "%s: channels %d -> %d -> %d (supported: input and output <= %d, hidden <= %d)",
-                who, Ci, Ch, Co, MV2_MAX_CIO, MV2_MAX_CH);
-    return 0;
-}
-
 template <int S, int TH, int TW>
 static int mv2_launch(Mv2Args a, hipStream_t st) {
     using G = Mv2Geo<S, TH, TW>;
@@ -263,19 +229,14 @@ static int mv2_launch(Mv2Args a, hipStream_t st) {
 using namespace osa;
 
 extern "C" size_t osa_mv2_block3d_packed_floats(int Ci, int Ch, int Co) {
-    return (Ci > 0 && Ch > 0 && Co > 0) ? mv2_packed_floats(Ci, Ch, Co) : 0;
+    return (Ci > 0 && Ch > 0 && Co > 0) ? mv2_packed_floats(27, Ci, Ch, Co) : 0;
 }
 
 extern "C" int osa_mv2_block3d_pack_f32(const float* w_expand, const float* w_dw, const float* w_project, const float* scale1, const float* shift1,
                                         const float* scale2, const float* shift2, const float* scale3, const float* shift3, float* packed,
                                         int Ci, int Ch, int Co, void* stream) {
-    OSA_REQUIRE(w_expand && w_dw && w_project && scale1 && shift1 && scale2 && shift2 && scale3 && shift3 && packed, "mv2_block3d_pack: NULL pointer");
-    if (int rc = mv2_check_channels("mv2_block3d_pack", Ci, Ch, Co)) return rc;
-    const int total = (int)mv2_packed_floats(Ci, Ch, Co);
-    hipLaunchKernelGGL(mv2_block3d_pack_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w_expand, w_dw, w_project, scale1, shift1, scale2, shift2,
-                       scale3, shift3, packed, Ci, Ch, Co);
-    OSA_LAUNCH_CHECK("mv2_block3d_pack");
-    return 0;
+    return mv2_pack<27>("mv2_block3d_pack", w_expand, w_dw, w_project, scale1, shift1, scale2, shift2, scale3, shift3, packed, Ci, Ch, Co, MV2_MAX_CIO, MV2_MAX_CH,
+                        (hipStream_t)stream);
 }
 
 extern "C" int osa_mv2_block3d_f32(const float* x, const float* packed, float* y, int B, int D, int H, int W, int Ci, int Ch, int Co, int stride, int residual,
@@ -283,7 +244,7 @@ extern "C" int osa_mv2_block3d_f32(const float* x, const float* packed, float* y
     OSA_REQUIRE(x && packed && y, "mv2_block3d: NULL pointer");
     OSA_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "mv2_block3d: bad dims");
     OSA_REQUIRE(stride == 1 || stride == 2, "mv2_block3d: stride %d (supported: 1 and 2)", stride);
-    if (int rc = mv2_check_channels("mv2_block3d", Ci, Ch, Co)) return rc;
+    if (int rc = mv2_check_channels("mv2_block3d", Ci, Ch, Co, MV2_MAX_CIO, MV2_MAX_CH)) return rc;
     OSA_REQUIRE(!residual || (stride == 1 && Ci == Co), "mv2_block3d: residual needs stride 1 and equal channels, got stride %d and %d -> %d", stride, Ci, Co);
     Mv2Args a{x, packed, y, B, D, H, W, Ci, Ch, Co, (D - 1) / stride + 1, (H - 1) / stride + 1, (W - 1) / stride + 1, residual ? 1 : 0, 0, 0, 0, 0};
     OSA_REQUIRE((long long)B * D * H * W * Ci < (1ll << 31) && (long long)B * a.Do * a.Ho * a.Wo * Co < (1ll << 31),

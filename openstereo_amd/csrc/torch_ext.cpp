@@ -180,6 +180,57 @@ at::Tensor mv2_block3d(const at::Tensor& x, const at::Tensor& packed, int64_t Ch
     return y;
 }
 
+// MobileStereoNet's 2-D inverted-residual block in eval mode with the caller's addend and ReLU (models/msnet/submodule.py:94-133,
+// MSNet2D.py:10-45; csrc/mv2_block2d.hip).  Inference ops like mv2_block3d.
+static Mv2Dims mv2d_pack_dims(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, at::TensorList bn) {
+    TORCH_CHECK(w1.dim() == 4 && wd.dim() == 4 && w3.dim() == 4 && w1.sizes().slice(2) == at::IntArrayRef({1, 1}) && w3.sizes().slice(2) == at::IntArrayRef({1, 1}) &&
+                wd.sizes().slice(1) == at::IntArrayRef({1, 3, 3}) && wd.size(0) == w1.size(0) && w3.size(1) == w1.size(0),
+                "mv2_block2d_pack: weights must be [Ch,Ci,1,1], [Ch,1,3,3] and [Co,Ch,1,1]");
+    const int64_t n[6] = {w1.size(0), w1.size(0), w1.size(0), w1.size(0), w3.size(0), w3.size(0)};
+    for (int i = 0; i < 6; ++i)
+        TORCH_CHECK(bn[i].dim() == 1 && bn[i].size(0) == n[i], "mv2_block2d_pack: folded BatchNorm vector ", i, " has shape ", bn[i].sizes(), ", expected [", n[i], "]");
+    return {(int)w1.size(1), (int)w1.size(0), (int)w3.size(0)};
+}
+at::Tensor mv2_block2d_pack_meta(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2,
+                                 const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
+    const Mv2Dims d = mv2d_pack_dims(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
+    return at::empty({(int64_t)osa_mv2_block2d_packed_floats(d.Ci, d.Ch, d.Co)}, w1.options().dtype(at::kFloat));
+}
+at::Tensor mv2_block2d_pack(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2,
+                            const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
+    at::Tensor t[9];
+    int i = 0;
+    for (const at::Tensor* s : {&w1, &wd, &w3, &s1, &b1, &s2, &b2, &s3, &b3}) t[i++] = gpu_f32(*s, "mv2_block2d_pack argument").detach().contiguous();
+    const Mv2Dims d = mv2d_pack_dims(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
+    auto packed = mv2_block2d_pack_meta(w1, wd, w3, s1, b1, s2, b2, s3, b3);
+    OSA_CALL(osa_mv2_block2d_pack_f32(fp(t[0]), fp(t[1]), fp(t[2]), fp(t[3]), fp(t[4]), fp(t[5]), fp(t[6]), fp(t[7]), fp(t[8]), packed.data_ptr<float>(), d.Ci, d.Ch, d.Co, cur_stream()));
+    return packed;
+}
+// -> logical [B, Co, Ho, Wo] with channels_last strides
+at::Tensor mv2_block2d_meta(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t stride, bool residual, const OptTensor& addend, bool) {
+    TORCH_CHECK(x.dim() == 4, "mv2_block2d: x must be [B,Ci,H,W], got ", x.sizes());
+    TORCH_CHECK(stride == 1 || stride == 2, "mv2_block2d: stride ", stride, " (supported: 1 and 2)");
+    TORCH_CHECK(Ch > 0 && Co > 0 && packed.dim() == 1 && packed.size(0) == (int64_t)osa_mv2_block2d_packed_floats((int)x.size(1), (int)Ch, (int)Co),
+                "mv2_block2d: packed parameters of ", packed.numel(), " floats do not belong to channels ", x.size(1), " -> ", Ch, " -> ", Co);
+    TORCH_CHECK(!residual || (stride == 1 && x.size(1) == Co), "mv2_block2d: residual needs stride 1 and equal channels");
+    auto out = [&](int64_t n) { return (n - 1) / stride + 1; };
+    const int64_t B = x.size(0), Ho = out(x.size(2)), Wo = out(x.size(3));
+    if (addend.has_value() && addend->defined())
+        TORCH_CHECK(addend->sizes() == at::IntArrayRef({B, Co, Ho, Wo}), "mv2_block2d: addend has shape ", addend->sizes(), ", expected [", B, ", ", Co, ", ", Ho, ", ", Wo, "]");
+    return at::empty({B, Ho, Wo, Co}, x.options().dtype(at::kFloat)).permute({0, 3, 1, 2});
+}
+at::Tensor mv2_block2d(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t stride, bool residual, const OptTensor& addend, bool relu) {
+    gpu_f32(x, "x"); gpu_f32(packed, "packed");
+    auto y = mv2_block2d_meta(x, packed, Ch, Co, stride, residual, addend, relu);
+    // a dense channels_last tensor is read in place; a contiguous one is converted (the hidden tensors, Ch channels wide, exist nowhere)
+    const at::Tensor xc = x.contiguous(at::MemoryFormat::ChannelsLast);
+    at::Tensor ad;
+    if (addend.has_value() && addend->defined()) ad = gpu_f32(*addend, "addend").contiguous(at::MemoryFormat::ChannelsLast);
+    OSA_CALL(osa_mv2_block2d_f32(fp(xc), fp(packed), ad.defined() ? fp(ad) : nullptr, y.data_ptr<float>(), (int)x.size(0), (int)x.size(2), (int)x.size(3), (int)x.size(1),
+                                 (int)Ch, (int)Co, (int)stride, residual ? 1 : 0, relu ? 1 : 0, cur_stream()));
+    return y;
+}
+
 // The interlaced cost volume of MSNet2D / StereoBase's InterlacedVolume in eval mode (csrc/interlaced_volume.hip).  Inference ops like mv2_block3d.
 struct IlvDims { int C, k2, k3, F; };
 static IlvDims ilv_pack_dims(const at::Tensor& w1, const at::Tensor& w2, const at::Tensor& w3, const at::Tensor& w4, at::TensorList bn) {
@@ -1325,6 +1376,8 @@ TORCH_LIBRARY(osa_native, m) {
     m.def("mr_volume(Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last=False) -> (Tensor, Tensor, Tensor)");
     m.def("mv2_block3d_pack(Tensor w_expand, Tensor w_dw, Tensor w_project, Tensor scale1, Tensor shift1, Tensor scale2, Tensor shift2, Tensor scale3, Tensor shift3) -> Tensor");
     m.def("mv2_block3d(Tensor x, Tensor packed, int hidden, int out_channels, int stride, bool residual) -> Tensor");
+    m.def("mv2_block2d_pack(Tensor w_expand, Tensor w_dw, Tensor w_project, Tensor scale1, Tensor shift1, Tensor scale2, Tensor shift2, Tensor scale3, Tensor shift3) -> Tensor");
+    m.def("mv2_block2d(Tensor x, Tensor packed, int hidden, int out_channels, int stride, bool residual, Tensor? addend, bool relu) -> Tensor");
     m.def("interlaced_volume_pack(Tensor w1, Tensor w2, Tensor w3, Tensor w4, Tensor scale1, Tensor shift1, Tensor scale2, Tensor shift2, Tensor scale3, Tensor shift3, Tensor scale4, Tensor shift4) -> Tensor");
     m.def("interlaced_volume(Tensor left, Tensor right, Tensor packed, int maxdisp, int k2, int k3, int features) -> Tensor");
     m.def("mr_volume_bwd(Tensor? dv0, Tensor? dv1, Tensor? dv2, Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -1400,6 +1453,8 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
     m.impl("mr_volume_bwd", &mr_volume_bwd);
     m.impl("mv2_block3d_pack", &mv2_block3d_pack);
     m.impl("mv2_block3d", &mv2_block3d);
+    m.impl("mv2_block2d_pack", &mv2_block2d_pack);
+    m.impl("mv2_block2d", &mv2_block2d);
     m.impl("interlaced_volume_pack", &interlaced_volume_pack);
     m.impl("interlaced_volume", &interlaced_volume);
     m.impl("concat_volume", &concat_volume);
@@ -1467,6 +1522,8 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
     m.impl("mr_volume_bwd", &mr_volume_bwd_meta);
     m.impl("mv2_block3d_pack", &mv2_block3d_pack_meta);
     m.impl("mv2_block3d", &mv2_block3d_meta);
+    m.impl("mv2_block2d_pack", &mv2_block2d_pack_meta);
+    m.impl("mv2_block2d", &mv2_block2d_meta);
     m.impl("interlaced_volume_pack", &interlaced_volume_pack_meta);
     m.impl("interlaced_volume", &interlaced_volume_meta);
     m.impl("concat_volume", &concat_volume_meta);

@@ -1,0 +1,212 @@
+"""GPU: MobileStereoNet's 2-D inverted-residual block as one launch (csrc/mv2_block2d.hip; osa_native.mv2_block2d; models/msnet.py grafted
+onto the restatement of tests/mv2_block2d_cases.py) by the tolerance rule stated there: every case in both memory formats, the fused
+addend and ReLU, the padding of the HIDDEN tensor, bit-reproducibility, independence of the batch size, hipGraph capture, an hourglass2D
+of such blocks (plain and through the mirror's fused-epilogue walk), the cases in which the block's own torch composition runs instead,
+and the whole MSNet2D with every block but the 3 -> 9 -> 32 one on the engine."""
+import copy
+import functools
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+import interlaced_volume_cases as IV
+import mv2_block2d_cases as M
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module", autouse=True)
+def grafted():
+    """the mirrors' forwards on the restatements' classes, as attach._graft_plan() puts them on the reference's"""
+    from openstereo_amd import attach
+    from openstereo_amd.models.msnet import MobileV2Residual2D, MSNet2D
+    attach._graft(M.Block, MobileV2Residual2D, ("forward", "reset_engine"), True)
+    attach._graft(IV.MV2, MobileV2Residual2D, ("forward", "reset_engine"), True)
+    attach._graft(IV.MSNet2D, MSNet2D, ("forward", "reset_engine"), True)
+    yield
+    attach.unpatch_reference()
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_block(case):
+    return M.make_block(case).to(DEV)
+
+
+class Entered:
+    """counts the calls of every block's `conv` Sequential under `module`: the torch composition ran"""
+
+    def __init__(self, module, cls=M.Block):
+        self.n = 0
+        self.hooks = [m.conv.register_forward_hook(self._hit) for m in module.modules() if isinstance(m, cls)]
+        assert self.hooks
+
+    def _hit(self, *a):
+        self.n += 1
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        for h in self.hooks:
+            h.remove()
+
+
+def fused(blk, x, run=None):
+    """eval, no grad: the fused launch, proven by `conv` never being entered"""
+    with Entered(blk) as e, torch.no_grad():
+        y = blk(x) if run is None else run(blk, x)
+    assert e.n == 0, "the torch composition ran instead of the fused kernel"
+    return y
+
+
+def cl(x):
+    return x.contiguous(memory_format=torch.channels_last)
+
+
+def cl_strides(shape):
+    """NHWC strides of a logical [B, C, H, W] (torch's own conversion leaves a 1 x 1 map's strides as they are)"""
+    B, C, H, W = shape
+    return (H * W * C, 1, W * C, C)
+
+
+@pytest.mark.parametrize("case", list(M.CASES))
+def test_every_case_by_the_rule_in_both_memory_formats(case):
+    x = M.make_input(case).to(DEV)
+    y_cl, y_nc = fused(gpu_block(case), cl(x)), fused(gpu_block(case), x.contiguous())
+    want = M.out_shape(case)
+    for y in (y_cl, y_nc):
+        assert y.dtype == torch.float32 and tuple(y.shape) == want and y.stride() == cl_strides(want)
+    assert torch.equal(y_cl, y_nc), f"{case}: the two memory formats of x give different bits"
+    M.check(case, y_cl, M.reference(case, torch.float64), M.reference(case, torch.float32))
+
+
+@pytest.mark.parametrize("case", ["dres", "s2odd"])
+def test_addend_and_relu_epilogues(case):
+    from openstereo_amd.models.msnet import mv2_block2d
+    blk, x, add = gpu_block(case), cl(M.make_input(case).to(DEV)), M.make_addend(case)
+    for with_add in (False, True):
+        for relu in (False, True):
+            a_cpu = add if with_add else None
+            r64 = M.reference(case, torch.float64, addend=None if a_cpu is None else a_cpu.double(), relu=relu)
+            r32 = M.reference(case, torch.float32, addend=a_cpu, relu=relu)
+            ys = [fused(blk, x, lambda b, t: mv2_block2d(b, t, fmt(a_cpu.to(DEV)) if with_add else None, relu))
+                  for fmt in ((cl, lambda t: t.contiguous()) if with_add and case == "dres" else (cl,))]
+            for y in ys:
+                assert y.stride() == cl_strides(M.out_shape(case))
+                assert torch.equal(y, ys[0]), "the two memory formats of the addend give different bits"
+                M.check(f"{case} addend={with_add} relu={relu}", y, r64, r32)
+            if relu:
+                assert float(ys[0].min()) == 0.0 and float((ys[0] == 0).float().mean()) >= 0.05
+
+
+@pytest.mark.parametrize("case", ["dres", "s2odd"])
+def test_the_hidden_tensor_is_padded_with_zeros_not_with_relu6_of_the_shift(case):
+    """x = 0: the hidden tensor is relu6(shift1) everywhere inside the map and ZERO around it, so the output is one value per channel in
+    the interior and another on every border; a kernel that pads x instead would return the interior value everywhere"""
+    x0 = torch.zeros_like(M.make_input(case))
+    r64, r32 = M.reference(case, torch.float64, x0), M.reference(case, torch.float32, x0)
+    y = fused(gpu_block(case), cl(x0.to(DEV)))
+    M.check(f"{case} x=0", y, r64, r32)
+    inner = y[:, :, 1:-1, 1:-1]
+    assert inner.numel() and torch.equal(inner, inner[:, :, :1, :1].expand_as(inner)), "the interior is not constant"
+    gap = (r64[:, :, 0, 0] - r64[:, :, 1, 1]).abs()                          # corner pixel against the interior, per channel
+    print(f"{case}: corner - interior up to {float(gap.max()):.2f}")
+    assert float(gap.max()) > 1.0, "the case does not tell the two paddings apart"
+    assert M.err(y[:, :, 0, 0] - y[:, :, 1, 1], r64[:, :, 0, 0] - r64[:, :, 1, 1]) <= 2 * M.FACTOR * max(M.err(r32, r64), 1e-7)
+    for border in (y[:, :, 0], y[:, :, -1], y[..., 0], y[..., -1]):
+        assert not torch.equal(border, inner[:, :, :1, 0].expand_as(border))
+
+
+def test_bits_do_not_depend_on_the_batch_the_run_or_a_graph_replay():
+    blk, x = gpu_block("dres"), cl(M.make_input("dres").to(DEV))
+    y = fused(blk, x)
+    assert torch.equal(fused(blk, x), y), "two calls differ"
+    assert torch.equal(fused(blk, cl(x[1:2])), y[1:2]), "batch element 1 alone differs from element 1 of the batch of two"
+    g = torch.cuda.CUDAGraph()
+    with torch.no_grad(), torch.cuda.graph(g):                             # one stream, no branches
+        yg = blk(x)
+    yg.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(yg, y), "the captured launch replays to other bits"
+
+
+class Hourglass2D(nn.Module):
+    """stereo/modeling/models/msnet/MSNet2D.py:10-45 restated from Block"""
+
+    def __init__(self, c):
+        super().__init__()
+        self.conv1, self.conv2 = M.Block(c, c * 2, 2, 2), M.Block(c * 2, c * 2, 1, 2)
+        self.conv3, self.conv4 = M.Block(c * 2, c * 4, 2, 2), M.Block(c * 4, c * 4, 1, 2)
+        self.conv5 = nn.Sequential(nn.ConvTranspose2d(c * 4, c * 2, 3, padding=1, output_padding=1, stride=2, bias=False), nn.BatchNorm2d(c * 2))
+        self.conv6 = nn.Sequential(nn.ConvTranspose2d(c * 2, c, 3, padding=1, output_padding=1, stride=2, bias=False), nn.BatchNorm2d(c))
+        self.redir1, self.redir2 = M.Block(c, c, 1, 2), M.Block(c * 2, c * 2, 1, 2)
+
+    def forward(self, x):
+        conv2 = self.conv2(self.conv1(x))
+        conv4 = self.conv4(self.conv3(conv2))
+        conv5 = F.relu(self.conv5(conv4) + self.redir2(conv2), inplace=True)
+        return F.relu(self.conv6(conv5) + self.redir1(x), inplace=True)
+
+
+def test_hourglass_of_grafted_blocks_plain_and_with_fused_epilogues():
+    """the channels_last results flow through torch's transposed convolutions unchanged; the mirror's walk (relu(deconv + redir) as the
+    redir block's epilogue) gives the same values; training and gradients keep the reference's forward"""
+    from openstereo_amd.models.msnet import hourglass2d
+    g = torch.Generator().manual_seed(5100)
+    net = M.seed_parameters(Hourglass2D(48), g).eval()
+    x = 2.0 * torch.randn(1, 48, 12, 20, generator=g)
+    with torch.no_grad():
+        r64 = copy.deepcopy(net).double()(x.double())
+        r32 = net(x)                                                         # the float32 figure of the rule: the torch composition (CPU tensors)
+    gnet, gx = copy.deepcopy(net).to(DEV), x.to(DEV)
+    M.check("hourglass2D, plain blocks", fused(gnet, gx), r64, r32)
+    M.check("hourglass2D, fused epilogues", fused(gnet, gx, hourglass2d), r64, r32)
+    with Entered(gnet) as e:                                                 # eval, but a gradient is required
+        gnet(gx.clone().requires_grad_())
+        assert e.n == 6
+        hourglass2d(gnet, gx.clone().requires_grad_())                       # the walk records the gradient too
+        assert e.n == 12
+    with Entered(gnet) as e, torch.no_grad():
+        gnet.train()(gx)
+    assert e.n == 6
+
+
+def test_fallbacks_run_the_original_composition():
+    blk, x = copy.deepcopy(gpu_block("dres")), M.make_input("dres").to(DEV)
+    with Entered(blk) as e, torch.no_grad():
+        with torch.autocast("cuda", dtype=torch.float16):
+            blk(x)
+        assert e.n == 1
+        assert blk.half()(x.half()).dtype == torch.float16 and e.n == 2
+    r1 = M.Block(48, 48, 1, 1).to(DEV).eval()                                # expanse_ratio == 1: five entries, no expansion
+    with Entered(r1) as e, torch.no_grad():
+        y = r1(x)
+    assert e.n == 1 and tuple(y.shape) == tuple(x.shape)
+    first = M.Block(3, 32, 2, 3).to(DEV).eval()                              # firstconv[0]: 3 -> 9 -> 32, no multiples of 8
+    with Entered(first) as e, torch.no_grad():
+        y = first(torch.randn(1, 3, 12, 20, device=DEV))
+    assert e.n == 1 and tuple(y.shape) == (1, 32, 6, 10)
+    dil = M.Block(48, 48, 1, 3, dilation=2).to(DEV).eval()                   # a dilated depthwise convolution
+    with Entered(dil) as e, torch.no_grad():
+        y = dil(x)
+    assert e.n == 1 and tuple(y.shape) == tuple(x.shape)
+
+
+def test_whole_msnet2d_with_every_fusable_block_on_the_engine():
+    """the restated MSNet2D with the model mirror and the block mirror grafted: the reference's disparity, and `conv` of a block is entered
+    only for the 3 -> 9 -> 32 block of `firstconv`, once per image (without the fused block every block of the model enters it)"""
+    net = IV.make_msnet2d().to(DEV)
+    L, R = (t.to(DEV) for t in IV.e2e_images())
+    with Entered(net, IV.MV2) as e, torch.no_grad():
+        d = net({"left": L, "right": R})["disp_pred"]
+    assert e.n == 2, f"`conv` of a block was entered {e.n} times"
+    want = torch.from_numpy(np.load(IV.GOLDEN)["e2e__disp_pred"])
+    assert want.std() > 0.5 and tuple(d.shape) == tuple(want.shape)
+    epe = float((d.cpu() - want).abs().mean())
+    print(f"MSNet2D with fused blocks: EPE {epe:.3e} px")
+    assert epe < 1e-3, epe
