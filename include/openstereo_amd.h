@@ -602,7 +602,8 @@ int osa_geo_rows_f32(const float* vol_ndhwc, float* rows, int B, int D, int H, i
 /* y[r, j] = (x[r,2j] + x[r,2j+1]) / 2, j < n/2   (F.avg_pool2d(.,[1,2],stride=[1,2]) along the row axis) */
 int osa_avgpool_rows_f32(const float* x, float* y, long long rows, int n, void* stream);
 /* One GRU-iteration lookup: out [B,(C+1)*(2r+1)*levels,H,W]; geo_levels[l] rows [B,H,W,C,geo_len[l]],
- * corr_levels[l] rows [B,H,W,corr_len[l]] (HOST arrays of device pointers / lengths); disp, coords_x [B,H,W]. */
+ * corr_levels[l] rows [B,H,W,corr_len[l]] (HOST arrays of device pointers / lengths); disp, coords_x [B,H,W].
+ * B*H*W*levels*(C+1) < 2^31 (pixel, row) pairs: the limit of the launcher all lookups share (this entry point had none before). */
 int osa_geo_lookup_f32(const float* const* geo_levels, const float* const* corr_levels,
                        const int* geo_len, const int* corr_len, int levels,
                        const float* disp, const float* coords_x, float* out,
@@ -614,8 +615,9 @@ int osa_geo_lookup_nhwc_f32(const float* const* geo_levels, const float* const* 
                             const float* disp, const float* coords_x, float* out, int out_cs,
                             int B, int H, int W, int C, int radius, void* stream);
 /* Gradient of osa_geo_lookup_f32 with respect to the pyramid levels (the disparity is detached in the reference's loop,
- * models/igev/igev_stereo.py:190): dgeo_levels / dcorr_levels have the shapes of geo_levels / corr_levels, are zero-filled and then
- * accumulated without atomics (every pixel owns its rows).  dout: [B,(C+1)*(2r+1)*levels,H,W]. */
+ * models/igev/igev_stereo.py:190): dgeo_levels / dcorr_levels have the shapes of geo_levels / corr_levels; every element is written
+ * (zeros included) as the sum, in ascending tap order, of the taps that land on it: no memset, no atomics (one wave per (pixel, level);
+ * one thread per element for radius > 4 or more than 256 upstream gradients per level).  dout: [B,(C+1)*(2r+1)*levels,H,W]. */
 int osa_geo_lookup_bwd_f32(float* const* dgeo_levels, float* const* dcorr_levels,
                            const int* geo_len, const int* corr_len, int levels,
                            const float* disp, const float* coords_x, const float* dout,
@@ -624,7 +626,8 @@ int osa_geo_lookup_bwd_f32(float* const* dgeo_levels, float* const* dcorr_levels
  * every lookup of the step (one per GRU iteration, igev_stereo.py:181-203); only the entries a lookup's taps reach, inside a window of 2r+3
  * positions per row of a (pixel, level), are touched (read-modify-write, no atomics: one lane per position, which sums its taps in ascending
  * order -- into zeros the result equals osa_geo_lookup_bwd_f32 bit for bit) -- instead of 22 dense gradients that autograd adds up.
- * radius <= 30, level lengths <= 2^19. */
+ * radius <= 30, level lengths <= 2^19, B*H*W*levels*(C+1) < 2^31 (pixel, row) pairs over ALL levels (the shared launcher's limit; it
+ * used to be counted per level). */
 int osa_geo_lookup_bwd_acc_f32(float* const* dgeo_levels, float* const* dcorr_levels,
                                const int* geo_len, const int* corr_len, int levels,
                                const float* disp, const float* coords_x, const float* dout,

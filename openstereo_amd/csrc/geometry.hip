@@ -83,13 +83,6 @@ __global__ __launch_bounds__(256) void avgpool_rows_kernel(const float* __restri
     y[i] = (p[0] + p[1]) * 0.5f;
 }
 
-struct LookupArgs {
-    const float* geo[4]; const float* corr[4];      // per level: rows [B,H,W,C,Dl] / [B,H,W,W2l]
-    const float* disp; const float* coords; float* out;
-    int B, H, W, C, levels, radius;
-    int Dl[4], Wl[4];
-};
-
 // Sampling position of one tap, with the reference's own float roundings: bilinear_sampler (igev/utils.py:61-79) maps the
 // pixel coordinate x to xgrid = 2 * x / (n - 1) - 1 and F.grid_sample(align_corners=True) maps it back with
 // ((xgrid + 1) / 2) * (n - 1); at n = 240 the round trip moves x by up to ~2e-5, which shifts the interpolation weights.
@@ -112,41 +105,117 @@ __device__ __forceinline__ float sample_row(const float* __restrict__ row, int n
     return a * t.w0 + b * t.w1;
 }
 
-__global__ __launch_bounds__(256) void geo_lookup_kernel(const LookupArgs p) {
-    const long long HW = (long long)p.H * p.W;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // pixel
-    if (i >= (long long)p.B * HW) return;
-    const long long b = i / HW, hw = i - b * HW;
-    const int taps = 2 * p.radius + 1;
+// ---- the lookup kernels.  Two lookups run on them: the single pyramid of StereoBase / IGEV (models/igev/geometry.py) and the multi-range
+// lookup of IGEV++ (models/igevpp/geometry.py:6-87): volume 0 with an averaged pyramid at disp / 2^l, volumes 1 and 2 (no pyramid) at
+// disp / 2 and disp / 4, the correlation pyramid at coords / 2^l - disp / 2^l; four output tensors (geo_feat0 / 1 / 2, init_corr).
+// The channels-last body is written once; the NCHW forward and the accumulating backward are written out for each lookup (see there).
+// A body works on the description of one row of a pixel, LookupSrc: the rows, their length, rows per pixel, an exact power-of-two scale,
+// the kind of position, where the taps go.  The lookups differ only in how row j finds that description.  That is the shared kernel's template
+// parameter P: MultiLookupArgs, a short list of sources passed by value (IGEV++), or LevelTable, where j = l * (C + 1) + c is row c of
+// level l (c == C: the correlation row) and the description is arithmetic over a table of levels.
+struct LookupSrc {
+    const float* rd;         // forward: the rows [B,H,W,rows,n]; backward: the upstream gradient of the tensor the rows' taps went to
+    float* wr;               // forward: the tensor the taps go to; backward: the gradient accumulator of the rows
+    int n, rows;             // row length; rows per pixel (C, or 1 for a correlation level)
+    int row0;                // list: index of the source's first row in a pixel's row list (ascending over the sources)
+    int ch0, nch;            // first channel of the source in its tensor; the tensor's channel count (NCHW) / channel stride (channels-last)
+    int pad_from;            // channels-last: the source that ends its tensor zero-fills channels pad_from .. nch - 1 (others: pad_from = nch)
+    float scale;             // 1, 1/2, 1/4, 1/8
+    int corr;                // 0: x = d * scale (geometry rows), 1: x = cx * scale - d * scale (correlation rows)
+};
+struct LookupRow { LookupSrc s; int c; };                                // a row's source and its index among the source's rows
+__device__ __forceinline__ float src_pos(const LookupSrc& s, float d, float cx) {
+    return s.corr ? cx * s.scale - d * s.scale : d * s.scale;
+}
+
+constexpr int MR_MAX_SRC = 10;                                           // 2 * levels + 2, levels <= 4
+struct MultiLookupArgs {
+    LookupSrc src[MR_MAX_SRC];
+    const float* disp; const float* coords;
+    int nsrc, rows_per_px, B, H, W, radius;
+};
+// the source of row j of a pixel.  The loop index is uniform, so the descriptors stay scalar loads from the kernel arguments and a lane picks
+// its own by selects (indexing src[] by a per-lane value would put the whole list into scratch memory)
+__device__ __forceinline__ LookupSrc src_of_row(const MultiLookupArgs& p, int j) {
+    LookupSrc s = p.src[0];
+#pragma unroll
+    for (int q = 1; q < MR_MAX_SRC; ++q)
+        if (q < p.nsrc && j >= p.src[q].row0) s = p.src[q];
+    return s;
+}
+__device__ __forceinline__ LookupRow row_of(const MultiLookupArgs& p, int j, int /*TAPS*/) {
+    LookupRow r;
+    r.s = src_of_row(p, j);
+    r.c = j - r.s.row0;
+    return r;
+}
+
+// RowT / TensorT: const float / float forward (rows read, `t` written), float / const float backward (gradient rows accumulated into, `t` the
+// upstream gradient read)
+template <class RowT, class TensorT>
+struct LevelTable {
+    RowT* geo[4]; RowT* corr[4];                    // per level: rows [B,H,W,C,Dl] / [B,H,W,Wl]
+    const float* disp; const float* coords; TensorT* t;
+    int B, H, W, C, levels, radius;
+    int Dl[4], Wl[4];
+    int rows_per_px, nch;                           // levels * (C + 1); channel count of `t` (NCHW) / its channel stride (channels-last)
+};
+template <class RowT, class TensorT>
+__device__ __forceinline__ LookupRow level_row(const LevelTable<RowT, TensorT>& p, int l, int c, int TAPS) {     // TAPS: the kernel's (0 = generic)
+    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
+    const bool corr = c == p.C;
     const int per_level = (p.C + 1) * taps;
-    const float d = p.disp[i], cx = p.coords[i];
-    float* o = p.out + (size_t)b * per_level * p.levels * HW + hw;
-    float scale = 1.f;
-    for (int l = 0; l < p.levels; ++l, scale *= 0.5f) {
-        const float* g = p.geo[l] + (size_t)i * p.C * p.Dl[l];
-        const float* crow = p.corr[l] + (size_t)i * p.Wl[l];
-        const float xg = d * scale, xc = cx * scale - d * scale;
-        for (int k = 0; k < taps; ++k) {                                    // tap position once, shared by the C volume rows
-            const float dx = (float)(k - p.radius);
-            const Tap tg = tap_of(dx + xg, p.Dl[l]);                        // geometry.py:36  x0 = dx + disp / 2^i
-            for (int c = 0; c < p.C; ++c)
-                o[((size_t)l * per_level + c * taps + k) * HW] = sample_row(g + (size_t)c * p.Dl[l], p.Dl[l], tg);
-            const Tap tc = tap_of(xc + dx, p.Wl[l]);                        // geometry.py:44  coords / 2^i - disp / 2^i + dx
-            o[((size_t)l * per_level + p.C * taps + k) * HW] = sample_row(crow, p.Wl[l], tc);
-        }
+    RowT* rows = corr ? p.corr[l] : p.geo[l];
+    LookupRow r;
+    if constexpr (std::is_const_v<RowT>) { r.s.rd = rows; r.s.wr = p.t; } else { r.s.rd = p.t; r.s.wr = rows; }
+    r.s.n = corr ? p.Wl[l] : p.Dl[l];
+    r.s.rows = corr ? 1 : p.C;
+    r.s.row0 = 0;
+    r.s.ch0 = l * per_level + (corr ? p.C * taps : 0);
+    r.s.nch = p.nch;
+    r.s.pad_from = corr && l == p.levels - 1 ? p.levels * per_level : p.nch;
+    r.s.scale = __int_as_float((127 - l) << 23);    // 2^-l from its exponent field, no division (the dense backward kernels multiply 0.5f l times)
+    r.s.corr = corr;
+    r.c = corr ? 0 : c;
+    return r;
+}
+template <class RowT, class TensorT>
+__device__ __forceinline__ LookupRow row_of(const LevelTable<RowT, TensorT>& p, int j, int TAPS) {
+    const int l = j / (p.C + 1);
+    return level_row(p, l, j - l * (p.C + 1), TAPS);
+}
+
+// NCHW (the training path), one thread per (row, pixel) (r5): a thread produces the 2r + 1 taps of ONE row (geometry row c of a source, or a
+// correlation row) of one pixel; consecutive threads are consecutive pixels of the same row, so every store instruction of a wave
+// writes consecutive floats of one output plane.  (One thread per PIXEL gave B*H*W threads -- 14720 at the StereoBase training map, 80 x 184,
+// under one wave per SIMD of the chip -- each walking 324 scattered loads: profiles/DESIGN_rounds1-5.md.)
+__global__ __launch_bounds__(256) void geo_lookup_rows_kernel(const MultiLookupArgs p) {
+    const long long HW = (long long)p.H * p.W, npix = (long long)p.B * HW;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= npix * p.rows_per_px) return;
+    const int j = (int)(t / npix);                                  // row (uniform over a workgroup unless it straddles a row boundary)
+    const long long i = t - (long long)j * npix;                    // pixel
+    const long long b = i / HW, hw = i - b * HW;
+    const LookupSrc s = src_of_row(p, j);
+    const int c = j - s.row0;
+    const int taps = 2 * p.radius + 1;
+    const float x = src_pos(s, p.disp[i], p.coords[i]);
+    const float* row = s.rd + ((size_t)i * s.rows + c) * s.n;
+    float* o = s.wr + ((size_t)b * s.nch + s.ch0 + (size_t)c * taps) * HW + hw;
+    for (int k = 0; k < taps; ++k) {
+        const float dx = (float)(k - p.radius);
+        o[(size_t)k * HW] = sample_row(row, s.n, tap_of(s.corr ? x + dx : dx + x, s.n));       // operand order of geometry.py:36 / :44, igevpp/geometry.py:43,49,57 / :65
     }
 }
 
-// The same NCHW lookup with one thread per (row, pixel) (r5): the per-pixel kernel above has B*H*W threads -- 14720 at the StereoBase training
-// map (80 x 184), under one wave per SIMD of the chip, each walking 324 scattered loads.  Here a thread produces the 2r + 1 taps of ONE row
-// (geometry row c of level l, or that level's correlation row) of one pixel; consecutive threads are consecutive pixels of the same row, so
-// every store instruction of a wave writes consecutive floats of one output plane.  Same tap_of / sample_row: same values.
-__global__ __launch_bounds__(256) void geo_lookup_rows_kernel(const LookupArgs p) {
+// The same over the level table.  Written out beside the list form: as one body over a row finder (like the channels-last kernel) it
+// gave the same values and was 0.2 - 0.7 % slower at 4 x 136 x 240 in every run (profiles/round11/lookup_one_definition.md).
+__global__ __launch_bounds__(256) void geo_lookup_level_rows_kernel(const LevelTable<const float, float> p) {
     const long long HW = (long long)p.H * p.W, npix = (long long)p.B * HW;
     const int rows_per_px = p.levels * (p.C + 1);
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= npix * rows_per_px) return;
-    const int j = (int)(t / npix);                                  // row (uniform over a workgroup unless it straddles a row boundary)
+    const int j = (int)(t / npix);                                  // row
     const long long i = t - (long long)j * npix;                    // pixel
     const long long b = i / HW, hw = i - b * HW;
     const int l = j / (p.C + 1), c = j - l * (p.C + 1);
@@ -159,7 +228,7 @@ __global__ __launch_bounds__(256) void geo_lookup_rows_kernel(const LookupArgs p
     const int n = is_corr ? p.Wl[l] : p.Dl[l];
     const float* row = is_corr ? p.corr[l] + (size_t)i * p.Wl[l] : p.geo[l] + ((size_t)i * p.C + c) * p.Dl[l];
     const float xg = d * scale, xc = cx * scale - d * scale;
-    float* o = p.out + (size_t)b * per_level * p.levels * HW + hw + ((size_t)l * per_level + (size_t)c * taps) * HW;
+    float* o = p.t + (size_t)b * per_level * p.levels * HW + hw + ((size_t)l * per_level + (size_t)c * taps) * HW;
     for (int k = 0; k < taps; ++k) {
         const float dx = (float)(k - p.radius);
         o[(size_t)k * HW] = sample_row(row, n, is_corr ? tap_of(xc + dx, n) : tap_of(dx + xg, n));      // operand order of geometry.py:36 / :44
@@ -197,74 +266,30 @@ __device__ __forceinline__ void row_taps_cl(const float* __restrict__ row, int n
 
 // Channels-last form for the engine's GRU loop: out [B,H,W,Cs] (Cs >= channels, the padding zero-filled), i.e. what the update
 // block's 1x1 convc1 reads -- the NCHW result of the kernel above had to be transposed every iteration (85 MB at 4 pairs).  One thread =
-// one (pixel, row): row j < levels * (C + 1) is geometry row c of level l or that level's correlation row, and produces the 2r + 1 taps of
-// its row = 2r + 1 consecutive output channels, so the threads of a pixel write its channel vector contiguously; 18x the threads of the
-// per-pixel kernel and 18 loads per thread instead of 324.  Same tap arithmetic (tap_of / sample_row), same values.
-template <int TAPS>
-__global__ __launch_bounds__(256) void geo_lookup_nhwc_kernel(const LookupArgs p, int Cs) {
-    const int rows_per_px = p.levels * (p.C + 1);
+// one (pixel, row): it produces the 2r + 1 taps of its row = 2r + 1 consecutive channels of the row's tensor, so the threads of a pixel write
+// its channel vector contiguously.  Same tap arithmetic (tap_of / sample_row), same values.
+template <int TAPS, class P>
+__global__ __launch_bounds__(256) void geo_lookup_nhwc_kernel(const P p) {
     const unsigned npix = (unsigned)p.B * p.H * p.W;                // host: B*H*W*rows < 2^31
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= npix * (unsigned)rows_per_px) return;
-    const unsigned i = t / (unsigned)rows_per_px;
-    const int j = (int)(t - i * (unsigned)rows_per_px);
-    const int l = j / (p.C + 1), c = j - l * (p.C + 1);
+    if (t >= npix * (unsigned)p.rows_per_px) return;
+    const unsigned i = t / (unsigned)p.rows_per_px;
+    const int j = (int)(t - i * (unsigned)p.rows_per_px);
+    const LookupRow r = row_of(p, j, TAPS);
+    const LookupSrc& s = r.s;
     const int taps = TAPS ? TAPS : 2 * p.radius + 1;
-    const float scale = 1.f / (float)(1 << l);                     // exact: the per-pixel kernel multiplies 0.5f l times
-    const float d = p.disp[i], cx = p.coords[i];
-    float* o = p.out + (size_t)i * Cs + (size_t)j * taps;
-    const bool is_corr = (c == p.C);
-    const int n = is_corr ? p.Wl[l] : p.Dl[l];
-    const float* row = is_corr ? p.corr[l] + (size_t)i * p.Wl[l] : p.geo[l] + ((size_t)i * p.C + c) * p.Dl[l];
-    const float x = is_corr ? (cx * scale - d * scale) : d * scale;
-    row_taps_cl<TAPS>(row, n, x, is_corr, p.radius, o);
-    if (j == rows_per_px - 1)
-        for (int k = rows_per_px * taps; k < Cs; ++k) p.out[(size_t)i * Cs + k] = 0.f;
+    const float x = src_pos(s, p.disp[i], p.coords[i]);
+    float* px = s.wr + (size_t)i * s.nch;
+    row_taps_cl<TAPS>(s.rd + ((size_t)i * s.rows + r.c) * s.n, s.n, x, s.corr != 0, p.radius, px + s.ch0 + r.c * taps);
+    if (r.c == s.rows - 1)
+        for (int k = s.pad_from; k < s.nch; ++k) px[k] = 0.f;
 }
 
-// Backward of the lookup w.r.t. the pyramid levels (the disparity is detached in the reference, igev_stereo.py:190): every pixel owns
-// its rows of every level, so a thread adds its taps into its own (zero-filled) rows -- no atomics, deterministic.
-struct LookupBwdArgs {
-    float* dgeo[4]; float* dcorr[4];
-    const float* disp; const float* coords; const float* dout;
-    int B, H, W, C, levels, radius;
-    int Dl[4], Wl[4];
-};
-__device__ __forceinline__ void scatter_row(float* __restrict__ row, int n, const Tap t, float g) {
-    if (t.x0 >= 0 && t.x0 < n) row[t.x0] += g * t.w0;
-    if (t.x0 + 1 >= 0 && t.x0 + 1 < n) row[t.x0 + 1] += g * t.w1;
-}
-__global__ __launch_bounds__(256) void geo_lookup_bwd_kernel(const LookupBwdArgs p) {
-    const long long HW = (long long)p.H * p.W;
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)p.B * HW) return;
-    const long long b = i / HW, hw = i - b * HW;
-    const int taps = 2 * p.radius + 1;
-    const int per_level = (p.C + 1) * taps;
-    const float d = p.disp[i], cx = p.coords[i];
-    const float* o = p.dout + (size_t)b * per_level * p.levels * HW + hw;
-    float scale = 1.f;
-    for (int l = 0; l < p.levels; ++l, scale *= 0.5f) {
-        float* g = p.dgeo[l] + (size_t)i * p.C * p.Dl[l];
-        float* crow = p.dcorr[l] + (size_t)i * p.Wl[l];
-        const float xg = d * scale, xc = cx * scale - d * scale;
-        for (int k = 0; k < taps; ++k) {
-            const float dx = (float)(k - p.radius);
-            const Tap tg = tap_of(dx + xg, p.Dl[l]);
-            for (int c = 0; c < p.C; ++c)
-                scatter_row(g + (size_t)c * p.Dl[l], p.Dl[l], tg, o[((size_t)l * per_level + c * taps + k) * HW]);
-            const Tap tc = tap_of(xc + dx, p.Wl[l]);
-            scatter_row(crow, p.Wl[l], tc, o[((size_t)l * per_level + p.C * taps + k) * HW]);
-        }
-    }
-}
-
-// r5: the same gradient in GATHER form.  The scatter kernel above gives every pixel ONE thread that read-modify-writes 324 scattered floats
-// of its (memset) rows: 0.54 ms per call at the 80 x 184 training map, 22 calls per StereoBase step (12 ms, the largest single item of the AMP
-// step's kernel census).  Here a thread owns one OUTPUT element (pixel, level, row, position j) and sums the taps that land on
-// it: tap k contributes dout_k * w0_k if x0_k == j and dout_k * w1_k if x0_k + 1 == j.  The taps are evaluated with the same tap_of() and
-// visited in the same order k = 0 .. 2r as the scatter kernel adds them, so the result is bit-identical; every element is written (zeros
-// included): no memset, no read-modify-write, consecutive threads write consecutive floats.
+// Dense backward of the lookup w.r.t. the pyramid levels (the disparity is detached in the reference, igev_stereo.py:190), in GATHER form
+// (r5): a thread owns one OUTPUT element (pixel, level, row, position j) and sums the taps that land on it: tap k contributes dout_k * w0_k
+// if x0_k == j and dout_k * w1_k if x0_k + 1 == j, with the forward's tap_of(), in ascending order k = 0 .. 2r.  Every element is written
+// (zeros included): no memset, no read-modify-write, consecutive threads write consecutive floats.  (The first form gave every pixel one
+// thread that scattered its 324 terms into memset rows: 0.54 ms per call at the 80 x 184 training map, profiles/DESIGN_rounds1-5.md.)
 struct LookupBwdGatherArgs {
     float* dgeo[4]; float* dcorr[4];
     const float* disp; const float* coords; const float* dout;
@@ -427,109 +452,9 @@ __device__ __forceinline__ void acc_row_window(int taps, int lane, int e, bool r
     *entry(j) += v;
 }
 
+// over the source list: all rows of a pixel in one grid
 template <int TAPS>      // TAPS = 2 * radius + 1 known at compile time (9 in every shipped config), 0 = generic
-__global__ __launch_bounds__(256) void geo_lookup_bwd_acc_kernel(const LookupBwdGatherArgs p) {
-    const unsigned HW = (unsigned)p.H * p.W;
-    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
-    const int G = taps + 2;                                              // <= 64 (host)
-    const int rpw = 64 / G;                                              // rows per wave
-    const unsigned nrows = (unsigned)p.B * HW * (p.C + 1);               // host: < 2^31
-    const int lane = threadIdx.x & 63;
-    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);          // host: waves * rpw < 2^32
-    const int l = blockIdx.y;
-    const int rw = lane / G, e = lane - rw * G;
-    const unsigned R = wave * (unsigned)rpw + rw;
-    const bool row_on = rw < rpw && R < nrows;                           // (no early return: every lane takes part in the shuffles)
-    const unsigned Rc = row_on ? R : 0u;
-    const unsigned i = Rc / (unsigned)(p.C + 1);                         // pixel
-    const int c = (int)(Rc - i * (unsigned)(p.C + 1));                   // row (c == C: the correlation row)
-    const unsigned b = i / HW, hw = i - b * HW;
-    const float scale = 1.f / (float)(1 << l);                          // exact: the dense kernels multiply 0.5f l times
-    const float d = p.disp[i], cx = p.coords[i];
-    const bool geo = c < p.C;
-    const float x = geo ? d * scale : cx * scale - d * scale;
-    const int n = geo ? p.Dl[l] : p.Wl[l];
-    const int per_level = (p.C + 1) * taps;
-    const float* o = p.dout + (size_t)b * per_level * p.levels * HW + hw + ((size_t)l * per_level + (size_t)c * taps) * HW;
-    acc_row_window(taps, lane, e, row_on, x, n, o, HW, [&](int pos) { return geo ? p.dgeo[l] + ((size_t)i * p.C + c) * n + pos : p.dcorr[l] + (size_t)i * n + pos; });
-}
-
-
-// ---- multi-range lookup of IGEV++ (models/igevpp/geometry.py:6-87): volume 0 with an averaged pyramid at disp / 2^l, volumes 1 and 2 (no
-// pyramid) at disp / 2 and disp / 4, the correlation pyramid at coords / 2^l - disp / 2^l; four output tensors (geo_feat0 / 1 / 2, init_corr).
-// A lookup is a short list of SOURCES passed by value: per source the rows, their length, rows per pixel, an exact power-of-two scale, the
-// kind of position and where its taps go.  The three kernels below are the rows / channels-last / accumulating kernels above over that list:
-// same tap_of / sample_row, same operand order, so a source gives bit for bit what the single-pyramid kernels give for the same rows.
-struct LookupSrc {
-    const float* rd;         // forward: the rows [B,H,W,rows,n]; backward: the upstream gradient of the tensor the rows' taps went to
-    float* wr;               // forward: the tensor the taps go to; backward: the gradient accumulator of the rows
-    int n, rows;             // row length; rows per pixel (C, or 1 for a correlation level)
-    int row0;                // index of the source's first row in a pixel's row list (ascending over the sources)
-    int ch0, nch;            // first channel of the source in its tensor; the tensor's channel count (NCHW) / channel stride (channels-last)
-    int pad_from;            // channels-last: the source that ends its tensor zero-fills channels pad_from .. nch - 1 (others: pad_from = nch)
-    float scale;             // 1, 1/2, 1/4, 1/8
-    int corr;                // 0: x = d * scale (geometry rows), 1: x = cx * scale - d * scale (correlation rows)
-};
-constexpr int MR_MAX_SRC = 10;                                           // 2 * levels + 2, levels <= 4
-struct MultiLookupArgs {
-    LookupSrc src[MR_MAX_SRC];
-    const float* disp; const float* coords;
-    int nsrc, rows_per_px, B, H, W, radius;
-};
-// the source of row j of a pixel.  The loop index is uniform, so the descriptors stay scalar loads from the kernel arguments and a lane picks
-// its own by selects (indexing src[] by a per-lane value would put the whole list into scratch memory)
-__device__ __forceinline__ LookupSrc src_of_row(const MultiLookupArgs& p, int j) {
-    LookupSrc s = p.src[0];
-#pragma unroll
-    for (int q = 1; q < MR_MAX_SRC; ++q)
-        if (q < p.nsrc && j >= p.src[q].row0) s = p.src[q];
-    return s;
-}
-__device__ __forceinline__ float src_pos(const LookupSrc& s, float d, float cx) {
-    return s.corr ? cx * s.scale - d * s.scale : d * s.scale;
-}
-
-// NCHW: one thread per (row, pixel), consecutive threads on consecutive pixels of one row (geo_lookup_rows_kernel)
-__global__ __launch_bounds__(256) void geo_lookup_mr_rows_kernel(const MultiLookupArgs p) {
-    const long long HW = (long long)p.H * p.W, npix = (long long)p.B * HW;
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= npix * p.rows_per_px) return;
-    const int j = (int)(t / npix);                                  // row (uniform over a workgroup unless it straddles a row boundary)
-    const long long i = t - (long long)j * npix;                    // pixel
-    const long long b = i / HW, hw = i - b * HW;
-    const LookupSrc s = src_of_row(p, j);
-    const int c = j - s.row0;
-    const int taps = 2 * p.radius + 1;
-    const float x = src_pos(s, p.disp[i], p.coords[i]);
-    const float* row = s.rd + ((size_t)i * s.rows + c) * s.n;
-    float* o = s.wr + ((size_t)b * s.nch + s.ch0 + (size_t)c * taps) * HW + hw;
-    for (int k = 0; k < taps; ++k) {
-        const float dx = (float)(k - p.radius);
-        o[(size_t)k * HW] = sample_row(row, s.n, tap_of(s.corr ? x + dx : dx + x, s.n));       // operand order of igevpp/geometry.py:43,49,57 / :65
-    }
-}
-
-// channels-last: one thread per (pixel, row), 2r + 1 contiguous channels of the row's tensor per thread (geo_lookup_nhwc_kernel)
-template <int TAPS>
-__global__ __launch_bounds__(256) void geo_lookup_mr_nhwc_kernel(const MultiLookupArgs p) {
-    const unsigned npix = (unsigned)p.B * p.H * p.W;                // host: B*H*W*rows < 2^31
-    const unsigned t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= npix * (unsigned)p.rows_per_px) return;
-    const unsigned i = t / (unsigned)p.rows_per_px;
-    const int j = (int)(t - i * (unsigned)p.rows_per_px);
-    const LookupSrc s = src_of_row(p, j);
-    const int c = j - s.row0;
-    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
-    const float x = src_pos(s, p.disp[i], p.coords[i]);
-    float* px = s.wr + (size_t)i * s.nch;
-    row_taps_cl<TAPS>(s.rd + ((size_t)i * s.rows + c) * s.n, s.n, x, s.corr != 0, p.radius, px + s.ch0 + c * taps);
-    if (c == s.rows - 1)
-        for (int k = s.pad_from; k < s.nch; ++k) px[k] = 0.f;
-}
-
-// accumulating backward with respect to every source: a row takes 2r + 3 lanes of a wave (geo_lookup_bwd_acc_kernel, see the comment there)
-template <int TAPS>
-__global__ __launch_bounds__(256) void geo_lookup_mr_bwd_acc_kernel(const MultiLookupArgs p) {
+__global__ __launch_bounds__(256) void geo_lookup_bwd_acc_kernel(const MultiLookupArgs p) {
     const unsigned HW = (unsigned)p.H * p.W;
     const int taps = TAPS ? TAPS : 2 * p.radius + 1;
     const int G = taps + 2;                                              // <= 64 (host)
@@ -551,81 +476,39 @@ __global__ __launch_bounds__(256) void geo_lookup_mr_bwd_acc_kernel(const MultiL
     acc_row_window(taps, lane, e, row_on, x, s.n, o, HW, [&](int pos) { return s.wr + ((size_t)i * s.rows + c) * s.n + pos; });
 }
 
+// over the level table: one grid slice per level, so the level is uniform and its table entries are scalar.  Written out beside the list
+// form: as one body over a row finder (like the channels-last kernel) it gave the same values and its median was above the parent's range
+// at 4 x 136 x 240 in three of four measurements, by up to 0.7 % (profiles/round11/lookup_one_definition.md).
+template <int TAPS>
+__global__ __launch_bounds__(256) void geo_lookup_level_bwd_acc_kernel(const LevelTable<float, const float> p) {
+    const unsigned HW = (unsigned)p.H * p.W;
+    const int taps = TAPS ? TAPS : 2 * p.radius + 1;
+    const int G = taps + 2;                                              // <= 64 (host)
+    const int rpw = 64 / G;                                              // rows per wave
+    const unsigned nrows = (unsigned)p.B * HW * (p.C + 1);               // host: < 2^31
+    const int lane = threadIdx.x & 63;
+    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);          // host: waves * rpw < 2^32
+    const int l = blockIdx.y;
+    const int rw = lane / G, e = lane - rw * G;
+    const unsigned R = wave * (unsigned)rpw + rw;
+    const bool row_on = rw < rpw && R < nrows;                           // (no early return: every lane takes part in the shuffles)
+    const unsigned Rc = row_on ? R : 0u;
+    const unsigned i = Rc / (unsigned)(p.C + 1);                         // pixel
+    const int c = (int)(Rc - i * (unsigned)(p.C + 1));                   // row (c == C: the correlation row)
+    const unsigned b = i / HW, hw = i - b * HW;
+    const float scale = 1.f / (float)(1 << l);                          // exact: the dense kernels multiply 0.5f l times
+    const float d = p.disp[i], cx = p.coords[i];
+    const bool geo = c < p.C;
+    const float x = geo ? d * scale : cx * scale - d * scale;
+    const int n = geo ? p.Dl[l] : p.Wl[l];
+    const int per_level = (p.C + 1) * taps;
+    const float* o = p.t + (size_t)b * per_level * p.levels * HW + hw + ((size_t)l * per_level + (size_t)c * taps) * HW;
+    acc_row_window(taps, lane, e, row_on, x, n, o, HW, [&](int pos) { return geo ? p.geo[l] + ((size_t)i * p.C + c) * n + pos : p.corr[l] + (size_t)i * n + pos; });
+}
+
 }  // namespace osa
 
 using namespace osa;
-
-extern "C" int osa_geo_lookup_bwd_f32(float* const* dgeo_levels, float* const* dcorr_levels,
-                                      const int* geo_len, const int* corr_len, int levels,
-                                      const float* disp, const float* coords_x, const float* dout,
-                                      int B, int H, int W, int C, int radius, void* stream) {
-    OSA_REQUIRE(dgeo_levels && dcorr_levels && geo_len && corr_len && disp && coords_x && dout, "geo_lookup_bwd: NULL pointer");
-    OSA_REQUIRE(levels >= 1 && levels <= 4, "geo_lookup_bwd: %d levels unsupported (1..4)", levels);
-    const long long total = (long long)B * H * W;
-    if (!exp_int("OSA_GEO_BWD_SCATTER", 0)) {                              // gather form (r5): one thread per output element, no memset
-        LookupBwdGatherArgs g;
-        long long end = 0;
-        for (int l = 0; l < levels; ++l) {
-            OSA_REQUIRE(dgeo_levels[l] && dcorr_levels[l] && geo_len[l] > 0 && corr_len[l] > 0, "geo_lookup_bwd: level %d missing", l);
-            g.dgeo[l] = dgeo_levels[l]; g.dcorr[l] = dcorr_levels[l]; g.Dl[l] = geo_len[l]; g.Wl[l] = corr_len[l];
-            end += total * C * geo_len[l]; g.seg_end[2 * l] = end;
-            end += total * corr_len[l]; g.seg_end[2 * l + 1] = end;
-        }
-        for (int q = 2 * levels; q < 8; ++q) g.seg_end[q] = end;
-        g.disp = disp; g.coords = coords_x; g.dout = dout;
-        g.B = B; g.H = H; g.W = W; g.C = C; g.levels = levels; g.radius = radius;
-        OSA_REQUIRE((end + 255) / 256 < (1ll << 31), "geo_lookup_bwd: grid too large");
-        if (2 * radius + 1 <= 9 && (C + 1) * (2 * radius + 1) <= 256 && exp_int("OSA_GEO_BWD_FORM", 2) == 2) {     // one wave per (pixel, level): every shipped config has radius 4
-            hipLaunchKernelGGL(geo_lookup_bwd_rows_kernel<9>, dim3((unsigned)((total + 3) / 4), levels), dim3(256), 0, (hipStream_t)stream, g);
-            OSA_LAUNCH_CHECK("geo_lookup_bwd (rows)");
-            return 0;
-        }
-        hipLaunchKernelGGL(geo_lookup_bwd_gather_kernel, dim3((unsigned)((end + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);
-        OSA_LAUNCH_CHECK("geo_lookup_bwd (gather)");
-        return 0;
-    }
-    LookupBwdArgs a;
-    for (int l = 0; l < levels; ++l) {
-        OSA_REQUIRE(dgeo_levels[l] && dcorr_levels[l] && geo_len[l] > 0 && corr_len[l] > 0, "geo_lookup_bwd: level %d missing", l);
-        a.dgeo[l] = dgeo_levels[l]; a.dcorr[l] = dcorr_levels[l]; a.Dl[l] = geo_len[l]; a.Wl[l] = corr_len[l];
-        hipError_t e = hipMemsetAsync(a.dgeo[l], 0, (size_t)total * C * geo_len[l] * sizeof(float), (hipStream_t)stream);
-        if (e == hipSuccess) e = hipMemsetAsync(a.dcorr[l], 0, (size_t)total * corr_len[l] * sizeof(float), (hipStream_t)stream);
-        OSA_REQUIRE(e == hipSuccess, "geo_lookup_bwd: memset failed: %s", hipGetErrorString(e));
-    }
-    a.disp = disp; a.coords = coords_x; a.dout = dout;
-    a.B = B; a.H = H; a.W = W; a.C = C; a.levels = levels; a.radius = radius;
-    hipLaunchKernelGGL(geo_lookup_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, a);
-    OSA_LAUNCH_CHECK("geo_lookup_bwd");
-    return 0;
-}
-
-extern "C" int osa_geo_lookup_bwd_acc_f32(float* const* dgeo_levels, float* const* dcorr_levels,
-                                          const int* geo_len, const int* corr_len, int levels,
-                                          const float* disp, const float* coords_x, const float* dout,
-                                          int B, int H, int W, int C, int radius, void* stream) {
-    OSA_REQUIRE(dgeo_levels && dcorr_levels && geo_len && corr_len && disp && coords_x && dout, "geo_lookup_bwd_acc: NULL pointer");
-    OSA_REQUIRE(levels >= 1 && levels <= 4 && radius >= 0 && C >= 1, "geo_lookup_bwd_acc: %d levels / radius %d unsupported", levels, radius);
-    LookupBwdGatherArgs g;
-    memset(&g, 0, sizeof(g));
-    for (int l = 0; l < levels; ++l) {
-        OSA_REQUIRE(dgeo_levels[l] && dcorr_levels[l] && geo_len[l] > 0 && corr_len[l] > 0, "geo_lookup_bwd_acc: level %d missing", l);
-        g.dgeo[l] = dgeo_levels[l]; g.dcorr[l] = dcorr_levels[l]; g.Dl[l] = geo_len[l]; g.Wl[l] = corr_len[l];
-    }
-    g.disp = disp; g.coords = coords_x; g.dout = dout;
-    g.B = B; g.H = H; g.W = W; g.C = C; g.levels = levels; g.radius = radius;
-    OSA_REQUIRE(radius <= 30, "geo_lookup_bwd_acc: radius %d: a row's window of 2r + 3 positions has to fit a wave", radius);
-    for (int l = 0; l < levels; ++l)
-        OSA_REQUIRE(geo_len[l] <= (1 << 19) && corr_len[l] <= (1 << 19), "geo_lookup_bwd_acc: level %d longer than 2^19", l);
-    const long long nrows = (long long)B * H * W * (C + 1);
-    const int rpw = 64 / (2 * radius + 3);                                  // rows per wave
-    const long long waves = (nrows + rpw - 1) / rpw;
-    OSA_REQUIRE(nrows > 0 && nrows < (1ll << 31) && (waves + 3) / 4 < (1ll << 30), "geo_lookup_bwd_acc: grid too large");
-    const dim3 grid((unsigned)((waves + 3) / 4), levels);
-    if (radius == 4) hipLaunchKernelGGL(geo_lookup_bwd_acc_kernel<9>, grid, dim3(256), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(geo_lookup_bwd_acc_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, g);
-    OSA_LAUNCH_CHECK("geo_lookup_bwd_acc");
-    return 0;
-}
 
 extern "C" int osa_allpairs_corr_f32(const float* fmap1, const float* fmap2, float* corr,
                                      int B, int C, int H, int W1, int W2, void* stream) {
@@ -659,60 +542,67 @@ extern "C" int osa_avgpool_rows_f32(const float* x, float* y, long long rows, in
     return 0;
 }
 
-extern "C" int osa_geo_lookup_nhwc_f32(const float* const* geo_levels, const float* const* corr_levels,
-                                       const int* geo_len, const int* corr_len, int levels,
-                                       const float* disp, const float* coords_x, float* out, int out_cs,
-                                       int B, int H, int W, int C, int radius, void* stream) {
-    OSA_REQUIRE(geo_levels && corr_levels && geo_len && corr_len && disp && coords_x && out, "geo_lookup_nhwc: NULL pointer");
-    OSA_REQUIRE(levels >= 1 && levels <= 4, "geo_lookup_nhwc: %d levels unsupported (1..4)", levels);
-    OSA_REQUIRE(out_cs >= levels * (C + 1) * (2 * radius + 1), "geo_lookup_nhwc: channel stride %d < %d channels", out_cs, levels * (C + 1) * (2 * radius + 1));
-    LookupArgs a;
-    for (int l = 0; l < levels; ++l) {
-        OSA_REQUIRE(geo_levels[l] && corr_levels[l] && geo_len[l] > 0 && corr_len[l] > 0, "geo_lookup_nhwc: level %d missing", l);
-        a.geo[l] = geo_levels[l]; a.corr[l] = corr_levels[l]; a.Dl[l] = geo_len[l]; a.Wl[l] = corr_len[l];
-    }
-    a.disp = disp; a.coords = coords_x; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.C = C; a.levels = levels; a.radius = radius;
-    const long long total = (long long)B * H * W * levels * (C + 1);
-    OSA_REQUIRE(total < (1ll << 31), "geo_lookup_nhwc: more than 2^31 (pixel, row) pairs");
-    if (radius == 4) hipLaunchKernelGGL(geo_lookup_nhwc_kernel<9>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, out_cs);
-    else hipLaunchKernelGGL(geo_lookup_nhwc_kernel<0>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, out_cs);
-    OSA_LAUNCH_CHECK("geo_lookup_nhwc");
-    return 0;
-}
-
-extern "C" int osa_geo_lookup_f32(const float* const* geo_levels, const float* const* corr_levels,
-                                  const int* geo_len, const int* corr_len, int levels,
-                                  const float* disp, const float* coords_x, float* out,
-                                  int B, int H, int W, int C, int radius, void* stream) {
-    OSA_REQUIRE(geo_levels && corr_levels && geo_len && corr_len && disp && coords_x && out, "geo_lookup: NULL pointer");
-    OSA_REQUIRE(levels >= 1 && levels <= 4, "geo_lookup: %d levels unsupported (1..4)", levels);
-    LookupArgs a;
-    for (int l = 0; l < levels; ++l) {
-        OSA_REQUIRE(geo_levels[l] && corr_levels[l] && geo_len[l] > 0 && corr_len[l] > 0, "geo_lookup: level %d missing", l);
-        a.geo[l] = geo_levels[l]; a.corr[l] = corr_levels[l]; a.Dl[l] = geo_len[l]; a.Wl[l] = corr_len[l];
-    }
-    a.disp = disp; a.coords = coords_x; a.out = out;
-    a.B = B; a.H = H; a.W = W; a.C = C; a.levels = levels; a.radius = radius;
-    const long long total = (long long)B * H * W;
-    if (exp_int("OSA_GEO_FWD_PIXEL", 0)) {                           // the r2 form: one thread per pixel (experiments build only)
-        hipLaunchKernelGGL(geo_lookup_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        const long long nthr = total * levels * (C + 1);
-        OSA_REQUIRE(cdiv(nthr, 256) > 0, "geo_lookup: grid too large");
-        hipLaunchKernelGGL(geo_lookup_rows_kernel, dim3(cdiv(nthr, 256)), dim3(256), 0, (hipStream_t)stream, a);
-    }
-    OSA_LAUNCH_CHECK("geo_lookup");
-    return 0;
-}
-
-// ---- multi-range lookup (IGEV++): the three entry points share one argument check and one source list
+// ---- the lookups' host side: one launcher for the three forms; a lookup fills its list or its level table and hands it over
 namespace {
-enum { MR_NCHW = 0, MR_NHWC = 1, MR_BWD = 2 };
+enum { LOOKUP_NCHW = 0, LOOKUP_NHWC = 1, LOOKUP_BWD = 2 };
+// slices: grid slices of the accumulating form, each with rows_per_px / slices rows per pixel (the level table: one per level)
+template <int FORM, class P>
+int lookup_launch(const char* who, const P& a, int slices, void* stream) {
+    const long long total = (long long)a.B * a.H * a.W * a.rows_per_px;    // (pixel, row) pairs
+    OSA_REQUIRE(total > 0, "%s: no (pixel, row) pairs (B, H, W, C > 0)", who);
+    OSA_REQUIRE(total < (1ll << 31), "%s: more than 2^31 (pixel, row) pairs", who);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if constexpr (FORM == LOOKUP_NCHW) {
+        if constexpr (std::is_same_v<P, MultiLookupArgs>) hipLaunchKernelGGL(geo_lookup_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(geo_lookup_level_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    } else if constexpr (FORM == LOOKUP_NHWC) {
+        if (a.radius == 4) hipLaunchKernelGGL((geo_lookup_nhwc_kernel<9, P>), grid, dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL((geo_lookup_nhwc_kernel<0, P>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    } else {
+        const int rpw = 64 / (2 * a.radius + 3);                            // rows per wave
+        const long long waves = (total / slices + rpw - 1) / rpw;
+        const dim3 bgrid((unsigned)((waves + 3) / 4), slices);
+        if constexpr (std::is_same_v<P, MultiLookupArgs>) {
+            if (a.radius == 4) hipLaunchKernelGGL(geo_lookup_bwd_acc_kernel<9>, bgrid, dim3(256), 0, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL(geo_lookup_bwd_acc_kernel<0>, bgrid, dim3(256), 0, (hipStream_t)stream, a);
+        } else {
+            if (a.radius == 4) hipLaunchKernelGGL(geo_lookup_level_bwd_acc_kernel<9>, bgrid, dim3(256), 0, (hipStream_t)stream, a);
+            else hipLaunchKernelGGL(geo_lookup_level_bwd_acc_kernel<0>, bgrid, dim3(256), 0, (hipStream_t)stream, a);
+        }
+    }
+    OSA_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// single pyramid.  RowT / TensorT as in LevelTable; cs: the channel stride of `t` (LOOKUP_NHWC)
+template <int FORM, class RowT, class TensorT>
+int pyramid_launch(const char* who, RowT* const* geo, RowT* const* corr, const int* geo_len, const int* corr_len, int levels,
+                   const float* disp, const float* coords_x, TensorT* t, int cs, int B, int H, int W, int C, int radius, void* stream) {
+    OSA_REQUIRE(geo && corr && geo_len && corr_len && disp && coords_x && t, "%s: NULL pointer", who);
+    if (FORM == LOOKUP_BWD) OSA_REQUIRE(levels >= 1 && levels <= 4 && radius >= 0 && C >= 1, "%s: %d levels / radius %d unsupported", who, levels, radius);
+    else OSA_REQUIRE(levels >= 1 && levels <= 4, "%s: %d levels unsupported (1..4)", who, levels);
+    const int channels = levels * (C + 1) * (2 * radius + 1);
+    if (FORM == LOOKUP_NHWC) OSA_REQUIRE(cs >= channels, "%s: channel stride %d < %d channels", who, cs, channels);
+    if (FORM == LOOKUP_BWD) OSA_REQUIRE(radius <= 30, "%s: radius %d: a row's window of 2r + 3 positions has to fit a wave", who, radius);
+    LevelTable<RowT, TensorT> a;
+    memset(&a, 0, sizeof(a));
+    for (int l = 0; l < levels; ++l) {
+        OSA_REQUIRE(geo[l] && corr[l] && geo_len[l] > 0 && corr_len[l] > 0, "%s: level %d missing", who, l);
+        if (FORM == LOOKUP_BWD) OSA_REQUIRE(geo_len[l] <= (1 << 19) && corr_len[l] <= (1 << 19), "%s: level %d longer than 2^19", who, l);
+        a.geo[l] = geo[l]; a.corr[l] = corr[l]; a.Dl[l] = geo_len[l]; a.Wl[l] = corr_len[l];
+    }
+    a.disp = disp; a.coords = coords_x; a.t = t;
+    a.B = B; a.H = H; a.W = W; a.C = C; a.levels = levels; a.radius = radius;
+    a.rows_per_px = levels * (C + 1);
+    a.nch = FORM == LOOKUP_NHWC ? cs : channels;
+    return lookup_launch<FORM>(who, a, levels, stream);
+}
+
+// multi-range lookup (IGEV++): the three entry points share one argument check and one source list.
 // SrcT / OutT: const float / float in the forward calls (rows read, tensors written), float / const float in the backward (rows accumulated
-// into, upstream gradients read).  t[4] = geo_feat0, geo_feat1, geo_feat2, init_corr (or their gradients); cs = their channel strides (MR_NHWC).
-template <class SrcT, class OutT>
-int mr_launch(int form, const char* who, SrcT* const* g0, SrcT* const* co, const int* g0_len, const int* co_len, int levels,
+// into, upstream gradients read).  t[4] = geo_feat0, geo_feat1, geo_feat2, init_corr (or their gradients); cs = their channel strides (LOOKUP_NHWC).
+template <int FORM, class SrcT, class OutT>
+int mr_launch(const char* who, SrcT* const* g0, SrcT* const* co, const int* g0_len, const int* co_len, int levels,
               SrcT* v1, int n1, SrcT* v2, int n2, const float* disp, const float* coords_x, OutT* const t[4], const int* cs,
               int B, int H, int W, int C, int radius, void* stream) {
     OSA_REQUIRE(g0 && co && g0_len && co_len && v1 && v2 && disp && coords_x && t[0] && t[1] && t[2] && t[3], "%s: NULL pointer", who);
@@ -723,9 +613,9 @@ int mr_launch(int form, const char* who, SrcT* const* g0, SrcT* const* co, const
     OSA_REQUIRE(n1 > 0 && n2 > 0, "%s: volume 1 / 2 of length %d / %d", who, n1, n2);
     const int taps = 2 * radius + 1;
     const int count[4] = {levels * C * taps, C * taps, C * taps, levels * taps};
-    if (form == MR_NHWC)
+    if (FORM == LOOKUP_NHWC)
         for (int q = 0; q < 4; ++q) OSA_REQUIRE(cs[q] >= count[q], "%s: channel stride %d < %d channels (tensor %d)", who, cs[q], count[q], q);
-    if (form == MR_BWD) {
+    if (FORM == LOOKUP_BWD) {
         OSA_REQUIRE(radius <= 30, "%s: radius %d: a row's window of 2r + 3 positions has to fit a wave", who, radius);
         for (int l = 0; l < levels; ++l) OSA_REQUIRE(g0_len[l] <= (1 << 19) && co_len[l] <= (1 << 19), "%s: level %d longer than 2^19", who, l);
         OSA_REQUIRE(n1 <= (1 << 19) && n2 <= (1 << 19), "%s: volume 1 / 2 longer than 2^19", who);
@@ -737,7 +627,7 @@ int mr_launch(int form, const char* who, SrcT* const* g0, SrcT* const* co, const
         LookupSrc& s = a.src[a.nsrc++];
         if constexpr (std::is_const_v<SrcT>) { s.rd = rows; s.wr = t[tensor]; } else { s.rd = t[tensor]; s.wr = rows; }
         s.n = n; s.rows = nrows; s.row0 = row0; s.ch0 = ch0; s.scale = scale; s.corr = corr;
-        s.nch = form == MR_NHWC ? cs[tensor] : count[tensor];
+        s.nch = FORM == LOOKUP_NHWC ? cs[tensor] : count[tensor];
         s.pad_from = ends_tensor ? count[tensor] : s.nch;
         row0 += nrows;
     };
@@ -747,25 +637,61 @@ int mr_launch(int form, const char* who, SrcT* const* g0, SrcT* const* co, const
     for (int l = 0; l < levels; ++l) put(co[l], co_len[l], 1, 3, l * taps, 1.f / (float)(1 << l), 1, l == levels - 1);       // coords / 2^l - disp / 2^l + dx
     a.rows_per_px = row0;
     a.disp = disp; a.coords = coords_x; a.B = B; a.H = H; a.W = W; a.radius = radius;
-    const long long total = (long long)B * H * W * row0;                   // (pixel, row) pairs
-    OSA_REQUIRE(total < (1ll << 31), "%s: more than 2^31 (pixel, row) pairs", who);
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (form == MR_NCHW) {
-        hipLaunchKernelGGL(geo_lookup_mr_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    } else if (form == MR_NHWC) {
-        if (radius == 4) hipLaunchKernelGGL(geo_lookup_mr_nhwc_kernel<9>, grid, dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(geo_lookup_mr_nhwc_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        const int rpw = 64 / (taps + 2);                                    // rows per wave
-        const long long waves = (total + rpw - 1) / rpw;
-        const dim3 bgrid((unsigned)((waves + 3) / 4));
-        if (radius == 4) hipLaunchKernelGGL(geo_lookup_mr_bwd_acc_kernel<9>, bgrid, dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(geo_lookup_mr_bwd_acc_kernel<0>, bgrid, dim3(256), 0, (hipStream_t)stream, a);
-    }
-    OSA_LAUNCH_CHECK(who);
-    return 0;
+    return lookup_launch<FORM>(who, a, 1, stream);
 }
 }  // namespace
+
+extern "C" int osa_geo_lookup_f32(const float* const* geo_levels, const float* const* corr_levels,
+                                  const int* geo_len, const int* corr_len, int levels,
+                                  const float* disp, const float* coords_x, float* out,
+                                  int B, int H, int W, int C, int radius, void* stream) {
+    return pyramid_launch<LOOKUP_NCHW>("geo_lookup", geo_levels, corr_levels, geo_len, corr_len, levels, disp, coords_x, out, 0, B, H, W, C, radius, stream);
+}
+
+extern "C" int osa_geo_lookup_nhwc_f32(const float* const* geo_levels, const float* const* corr_levels,
+                                       const int* geo_len, const int* corr_len, int levels,
+                                       const float* disp, const float* coords_x, float* out, int out_cs,
+                                       int B, int H, int W, int C, int radius, void* stream) {
+    return pyramid_launch<LOOKUP_NHWC>("geo_lookup_nhwc", geo_levels, corr_levels, geo_len, corr_len, levels, disp, coords_x, out, out_cs, B, H, W, C, radius, stream);
+}
+
+extern "C" int osa_geo_lookup_bwd_acc_f32(float* const* dgeo_levels, float* const* dcorr_levels,
+                                          const int* geo_len, const int* corr_len, int levels,
+                                          const float* disp, const float* coords_x, const float* dout,
+                                          int B, int H, int W, int C, int radius, void* stream) {
+    return pyramid_launch<LOOKUP_BWD>("geo_lookup_bwd_acc", dgeo_levels, dcorr_levels, geo_len, corr_len, levels, disp, coords_x, dout, 0, B, H, W, C, radius, stream);
+}
+
+// the dense backward has its own kernels and its own level table
+extern "C" int osa_geo_lookup_bwd_f32(float* const* dgeo_levels, float* const* dcorr_levels,
+                                      const int* geo_len, const int* corr_len, int levels,
+                                      const float* disp, const float* coords_x, const float* dout,
+                                      int B, int H, int W, int C, int radius, void* stream) {
+    OSA_REQUIRE(dgeo_levels && dcorr_levels && geo_len && corr_len && disp && coords_x && dout, "geo_lookup_bwd: NULL pointer");
+    OSA_REQUIRE(levels >= 1 && levels <= 4, "geo_lookup_bwd: %d levels unsupported (1..4)", levels);
+    LookupBwdGatherArgs g;
+    memset(&g, 0, sizeof(g));
+    const long long total = (long long)B * H * W;
+    long long end = 0;
+    for (int l = 0; l < levels; ++l) {
+        OSA_REQUIRE(dgeo_levels[l] && dcorr_levels[l] && geo_len[l] > 0 && corr_len[l] > 0, "geo_lookup_bwd: level %d missing", l);
+        g.dgeo[l] = dgeo_levels[l]; g.dcorr[l] = dcorr_levels[l]; g.Dl[l] = geo_len[l]; g.Wl[l] = corr_len[l];
+        end += total * C * geo_len[l]; g.seg_end[2 * l] = end;
+        end += total * corr_len[l]; g.seg_end[2 * l + 1] = end;
+    }
+    for (int q = 2 * levels; q < 8; ++q) g.seg_end[q] = end;
+    g.disp = disp; g.coords = coords_x; g.dout = dout;
+    g.B = B; g.H = H; g.W = W; g.C = C; g.levels = levels; g.radius = radius;
+    OSA_REQUIRE((end + 255) / 256 < (1ll << 31), "geo_lookup_bwd: grid too large");
+    if (2 * radius + 1 <= 9 && (C + 1) * (2 * radius + 1) <= 256 && exp_int("OSA_GEO_BWD_FORM", 2) == 2) {     // one wave per (pixel, level): every shipped config has radius 4
+        hipLaunchKernelGGL(geo_lookup_bwd_rows_kernel<9>, dim3((unsigned)((total + 3) / 4), levels), dim3(256), 0, (hipStream_t)stream, g);
+        OSA_LAUNCH_CHECK("geo_lookup_bwd (rows)");
+        return 0;
+    }
+    hipLaunchKernelGGL(geo_lookup_bwd_gather_kernel, dim3((unsigned)((end + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g);   // one thread per output element
+    OSA_LAUNCH_CHECK("geo_lookup_bwd (gather)");
+    return 0;
+}
 
 extern "C" int osa_geo_lookup_mr_f32(const float* const* geo0_levels, const float* const* corr_levels,
                                      const int* geo0_len, const int* corr_len, int levels,
@@ -774,7 +700,7 @@ extern "C" int osa_geo_lookup_mr_f32(const float* const* geo0_levels, const floa
                                      float* geo_feat0, float* geo_feat1, float* geo_feat2, float* init_corr,
                                      int B, int H, int W, int C, int radius, void* stream) {
     float* const t[4] = {geo_feat0, geo_feat1, geo_feat2, init_corr};
-    return mr_launch<const float, float>(MR_NCHW, "geo_lookup_mr", geo0_levels, corr_levels, geo0_len, corr_len, levels, geo1, geo1_len, geo2, geo2_len,
+    return mr_launch<LOOKUP_NCHW, const float, float>("geo_lookup_mr", geo0_levels, corr_levels, geo0_len, corr_len, levels, geo1, geo1_len, geo2, geo2_len,
                                          disp, coords_x, t, nullptr, B, H, W, C, radius, stream);
 }
 
@@ -787,7 +713,7 @@ extern "C" int osa_geo_lookup_mr_nhwc_f32(const float* const* geo0_levels, const
                                           int B, int H, int W, int C, int radius, void* stream) {
     float* const t[4] = {geo_feat0, geo_feat1, geo_feat2, init_corr};
     const int cs[4] = {cs0, cs1, cs2, cs_corr};
-    return mr_launch<const float, float>(MR_NHWC, "geo_lookup_mr_nhwc", geo0_levels, corr_levels, geo0_len, corr_len, levels, geo1, geo1_len, geo2, geo2_len,
+    return mr_launch<LOOKUP_NHWC, const float, float>("geo_lookup_mr_nhwc", geo0_levels, corr_levels, geo0_len, corr_len, levels, geo1, geo1_len, geo2, geo2_len,
                                          disp, coords_x, t, cs, B, H, W, C, radius, stream);
 }
 
@@ -798,6 +724,6 @@ extern "C" int osa_geo_lookup_mr_bwd_acc_f32(float* const* dgeo0_levels, float* 
                                              const float* dfeat0, const float* dfeat1, const float* dfeat2, const float* dcorr_out,
                                              int B, int H, int W, int C, int radius, void* stream) {
     const float* const t[4] = {dfeat0, dfeat1, dfeat2, dcorr_out};
-    return mr_launch<float, const float>(MR_BWD, "geo_lookup_mr_bwd_acc", dgeo0_levels, dcorr_levels, geo0_len, corr_len, levels, dgeo1, geo1_len, dgeo2, geo2_len,
+    return mr_launch<LOOKUP_BWD, float, const float>("geo_lookup_mr_bwd_acc", dgeo0_levels, dcorr_levels, geo0_len, corr_len, levels, dgeo1, geo1_len, dgeo2, geo2_len,
                                          disp, coords_x, t, nullptr, B, H, W, C, radius, stream);
 }

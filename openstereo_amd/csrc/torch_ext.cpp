@@ -684,30 +684,32 @@ void gru_gates_q_bwd(const at::Tensor& z, const at::Tensor& qpre, const c10::opt
     OSA_CALL(osa_gru_gates_q_bwd(&a, &b, fpo(bq), &c, &d, &e, &f, &g, &i, (long long)h.size(0) * h.size(2) * h.size(3), (int)h.size(1), cur_stream()));
 }
 
+// the row tensors of a lookup (pyramid levels, IGEV++ sources; at most 10): fp32 on the GPU, the last axis the row.
+// The first `split` tensors are called `first` in the error message, the others `rest`.
+struct RowList { float* ptr[10]; int len[10]; };
+inline RowList row_list(at::TensorList ts, size_t split, const char* first, const char* rest) {
+    RowList v;
+    TORCH_CHECK(ts.size() <= 10, "row_list: ", ts.size(), " row tensors, at most 10");
+    for (size_t q = 0; q < ts.size(); ++q) { v.ptr[q] = gpu_f32(ts[q], q < split ? first : rest).data_ptr<float>(); v.len[q] = (int)ts[q].size(-1); }
+    return v;
+}
+
 // geometry-encoding lookup of the GRU loop (igev/geometry.py, stereobase/gru_blocks.py:170-231): `levels` = the geo pyramid followed by the corr pyramid
 // (rows of [.., len_l] floats); forward writes out [B, (C + 1)(2r + 1) L, H, W], backward writes the gradients of every level (same shapes).
 void geo_lookup(at::TensorList levels, const at::Tensor& disp, const at::Tensor& coords_x, at::Tensor out, int64_t C, int64_t radius) {
     const size_t L = levels.size() / 2;
     TORCH_CHECK(L >= 1 && L <= 4 && levels.size() == 2 * L, "geo_lookup: levels = geo pyramid + corr pyramid, 1..4 levels each");
     gpu_f32(disp, "disp"); gpu_f32(coords_x, "coords_x"); gpu_f32(out, "out");
-    const float* gp[4]; const float* cp[4]; int gl[4], cl[4];
-    for (size_t l = 0; l < L; ++l) {
-        gp[l] = fp(gpu_f32(levels[l], "geo level")); cp[l] = fp(gpu_f32(levels[L + l], "corr level"));
-        gl[l] = (int)levels[l].size(-1); cl[l] = (int)levels[L + l].size(-1);
-    }
-    OSA_CALL(osa_geo_lookup_f32(gp, cp, gl, cl, (int)L, fp(disp), fp(coords_x), out.data_ptr<float>(), (int)disp.size(0), (int)disp.size(1), (int)disp.size(2), (int)C, (int)radius, cur_stream()));
+    const RowList v = row_list(levels, L, "geo level", "corr level");
+    OSA_CALL(osa_geo_lookup_f32(v.ptr, v.ptr + L, v.len, v.len + L, (int)L, fp(disp), fp(coords_x), out.data_ptr<float>(), (int)disp.size(0), (int)disp.size(1), (int)disp.size(2), (int)C, (int)radius, cur_stream()));
 }
 static void geo_lookup_bwd_any(bool acc, at::TensorList dlevels, const at::Tensor& disp, const at::Tensor& coords_x, const at::Tensor& dout, int64_t C, int64_t radius) {
     const size_t L = dlevels.size() / 2;
     TORCH_CHECK(L >= 1 && L <= 4 && dlevels.size() == 2 * L, "geo_lookup_bwd: dlevels = gradients of the geo pyramid + of the corr pyramid");
     gpu_f32(disp, "disp"); gpu_f32(coords_x, "coords_x"); gpu_f32(dout, "dout");
-    float* gp[4]; float* cp[4]; int gl[4], cl[4];
-    for (size_t l = 0; l < L; ++l) {
-        gp[l] = gpu_f32(dlevels[l], "dgeo level").data_ptr<float>(); cp[l] = gpu_f32(dlevels[L + l], "dcorr level").data_ptr<float>();
-        gl[l] = (int)dlevels[l].size(-1); cl[l] = (int)dlevels[L + l].size(-1);
-    }
-    if (acc) OSA_CALL(osa_geo_lookup_bwd_acc_f32(gp, cp, gl, cl, (int)L, fp(disp), fp(coords_x), fp(dout), (int)disp.size(0), (int)disp.size(1), (int)disp.size(2), (int)C, (int)radius, cur_stream()));
-    else OSA_CALL(osa_geo_lookup_bwd_f32(gp, cp, gl, cl, (int)L, fp(disp), fp(coords_x), fp(dout), (int)disp.size(0), (int)disp.size(1), (int)disp.size(2), (int)C, (int)radius, cur_stream()));
+    const RowList v = row_list(dlevels, L, "dgeo level", "dcorr level");
+    if (acc) OSA_CALL(osa_geo_lookup_bwd_acc_f32(v.ptr, v.ptr + L, v.len, v.len + L, (int)L, fp(disp), fp(coords_x), fp(dout), (int)disp.size(0), (int)disp.size(1), (int)disp.size(2), (int)C, (int)radius, cur_stream()));
+    else OSA_CALL(osa_geo_lookup_bwd_f32(v.ptr, v.ptr + L, v.len, v.len + L, (int)L, fp(disp), fp(coords_x), fp(dout), (int)disp.size(0), (int)disp.size(1), (int)disp.size(2), (int)C, (int)radius, cur_stream()));
 }
 void geo_lookup_bwd(at::TensorList dlevels, const at::Tensor& disp, const at::Tensor& coords_x, const at::Tensor& dout, int64_t C, int64_t radius) {
     geo_lookup_bwd_any(false, dlevels, disp, coords_x, dout, C, radius);
@@ -836,12 +838,8 @@ void geo_lookup_nhwc(at::TensorList levels, const at::Tensor& disp, const at::Te
     const size_t L = levels.size() / 2;
     TORCH_CHECK(L >= 1 && L <= 4 && levels.size() == 2 * L && bhw.size() == 3, "geo_lookup_nhwc: levels = geo pyramid + corr pyramid (1..4 levels each), bhw = [B, H, W]");
     gpu_f32(disp, "disp"); gpu_f32(coords_x, "coords_x"); gpu_f32(out, "out");
-    const float* gp[4]; const float* cp[4]; int gl[4], cl[4];
-    for (size_t l = 0; l < L; ++l) {
-        gp[l] = fp(gpu_f32(levels[l], "geo level")); cp[l] = fp(gpu_f32(levels[L + l], "corr level"));
-        gl[l] = (int)levels[l].size(-1); cl[l] = (int)levels[L + l].size(-1);
-    }
-    OSA_CALL(osa_geo_lookup_nhwc_f32(gp, cp, gl, cl, (int)L, fp(disp), fp(coords_x), out.data_ptr<float>(), (int)out_cs, (int)bhw[0], (int)bhw[1], (int)bhw[2], (int)C, (int)radius,
+    const RowList v = row_list(levels, L, "geo level", "corr level");
+    OSA_CALL(osa_geo_lookup_nhwc_f32(v.ptr, v.ptr + L, v.len, v.len + L, (int)L, fp(disp), fp(coords_x), out.data_ptr<float>(), (int)out_cs, (int)bhw[0], (int)bhw[1], (int)bhw[2], (int)C, (int)radius,
                                      cur_stream()));
 }
 
@@ -854,19 +852,18 @@ static void geo_lookup_mr_any(int form, const char* who, at::TensorList sources,
     TORCH_CHECK(L >= 1 && L <= 4 && sources.size() == 2 * L + 2 && outs.size() == 4 && (form != 1 || cs.size() == 4), who,
                 ": sources = volume-0 levels + volume 1 + volume 2 + corr levels (1..4 levels), four outs");
     gpu_f32(disp, "disp"); gpu_f32(coords_x, "coords_x");
-    float* sp[10]; int sl[10]; float* op[4];
-    for (size_t q = 0; q < 2 * L + 2; ++q) { sp[q] = gpu_f32(sources[q], "source").data_ptr<float>(); sl[q] = (int)sources[q].size(-1); }
+    const RowList v = row_list(sources, 2 * L + 2, "source", "source");
+    float* op[4];
     for (size_t q = 0; q < 4; ++q) op[q] = gpu_f32(outs[q], "out").data_ptr<float>();
-    float** g0 = sp; float** co = sp + L + 2;
-    const int* g0l = sl; const int* col = sl + L + 2;
+    const size_t K = L + 2;                                             // the corr levels follow volume 2
     if (form == 0)
-        OSA_CALL(osa_geo_lookup_mr_f32(g0, co, g0l, col, (int)L, sp[L], sl[L], sp[L + 1], sl[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
+        OSA_CALL(osa_geo_lookup_mr_f32(v.ptr, v.ptr + K, v.len, v.len + K, (int)L, v.ptr[L], v.len[L], v.ptr[L + 1], v.len[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
                                        B, H, W, (int)C, (int)radius, cur_stream()));
     else if (form == 1)
-        OSA_CALL(osa_geo_lookup_mr_nhwc_f32(g0, co, g0l, col, (int)L, sp[L], sl[L], sp[L + 1], sl[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
+        OSA_CALL(osa_geo_lookup_mr_nhwc_f32(v.ptr, v.ptr + K, v.len, v.len + K, (int)L, v.ptr[L], v.len[L], v.ptr[L + 1], v.len[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
                                             (int)cs[0], (int)cs[1], (int)cs[2], (int)cs[3], B, H, W, (int)C, (int)radius, cur_stream()));
     else
-        OSA_CALL(osa_geo_lookup_mr_bwd_acc_f32(g0, co, g0l, col, (int)L, sp[L], sl[L], sp[L + 1], sl[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
+        OSA_CALL(osa_geo_lookup_mr_bwd_acc_f32(v.ptr, v.ptr + K, v.len, v.len + K, (int)L, v.ptr[L], v.len[L], v.ptr[L + 1], v.len[L + 1], fp(disp), fp(coords_x), op[0], op[1], op[2], op[3],
                                                B, H, W, (int)C, (int)radius, cur_stream()));
 }
 void geo_lookup_mr(at::TensorList sources, const at::Tensor& disp, const at::Tensor& coords_x, at::TensorList outs, int64_t C, int64_t radius) {
