@@ -3,11 +3,11 @@
     python -m openstereo_amd.build          # incremental
     python -m openstereo_amd.build --force  # rebuild everything
 
-Produces openstereo_amd/lib/libopenstereo_amd.so.  hipcc cross-compiles for gfx950 without a
-GPU, so this runs in the CPU-only dev container; the .so is git-ignored but travels with gpurun.
+Produces openstereo_amd/lib/libopenstereo_amd.so (git-ignored); hipcc cross-compiles for gfx950, so no GPU is needed.
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -58,8 +58,7 @@ def lib_path() -> str:
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "osa_common.h"), os.path.join(CSRC, "conv_kernel.h"), os.path.join(CSRC, "conv_march.h"), os.path.join(CSRC, "conv_march_s2.h"), os.path.join(CSRC, "conv_deconv_walk.h"), os.path.join(CSRC, "conv_inst.h"), os.path.join(CSRC, "conv_inst_impl.h"), os.path.join(CSRC, "conv_cfgs.def"), os.path.join(CSRC, "head_common.h"), os.path.join(CSRC, "mr_volume.h"),
-               os.path.join(HERE, "..", "include", "openstereo_amd.h")]
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.def"))) + [os.path.join(HERE, "..", "include", "openstereo_amd.h")]   # every header, of every source
 
     def compile_one(src: str) -> str:
         s = os.path.join(CSRC, src)
@@ -71,7 +70,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             subprocess.check_call(cmd)
         return o
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), int(os.environ.get("MAX_JOBS", 16)), os.cpu_count() or 1)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     out = lib_path()
     if force or _stale(out, objs):

@@ -35,7 +35,7 @@
 namespace osa {
 
 constexpr int ILV_NT = 512, ILV_NW = ILV_NT / 64, ILV_TH = 8, ILV_TW = 16, ILV_K1 = 8, ILV_MAXF = 16;
-typedef float ilv_f32x4 __attribute__((ext_vector_type(4)));
+typedef osa_f32x4_t ilv_f32x4;
 
 struct IlvArgs {
     const float* fl; const float* fr; const float* pk; float* out;
@@ -45,12 +45,6 @@ struct IlvArgs {
 static inline size_t ilv_packed_floats(int k2, int k3, int F) { return 1280 + 4608 * (size_t)(k2 + k3) + 18 * (size_t)F; }
 static inline bool ilv_supported(int C, int k2, int k3) { return (C == 32 && k2 == 4 && k3 == 2) || (C == 96 && k2 == 8 && k3 == 3); }
 
-__device__ __forceinline__ ilv_f32x4 ilv_mfma4(const float4 a, const float4 b, ilv_f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c, 0, 0, 0);
-}
 __device__ __forceinline__ float4 ilv_affine_relu(const ilv_f32x4 a, const float* s, const float* t, bool inside) {
     if (!inside) return make_float4(0.f, 0.f, 0.f, 0.f);
     return make_float4(fmaxf(fmaf(a[0], s[0], t[0]), 0.f), fmaxf(fmaf(a[1], s[1], t[1]), 0.f), fmaxf(fmaf(a[2], s[2], t[2]), 0.f), fmaxf(fmaf(a[3], s[3], t[3]), 0.f));
@@ -168,7 +162,7 @@ __global__ __launch_bounds__(ILV_NT) void interlaced_volume_kernel(const IlvArgs
 #pragma unroll
                 for (int j = 0; j < NT2; ++j) {
                     if (wave + ILV_NW * j >= 2 * NB2) break;
-                    acc2[j] = ilv_mfma4(a, *reinterpret_cast<const float4*>(A1s + ao2[j] + ((tap / 3) * R1W + tap % 3) * 16), acc2[j]);
+                    acc2[j] = mfma_k16(a, *reinterpret_cast<const float4*>(A1s + ao2[j] + ((tap / 3) * R1W + tap % 3) * 16), acc2[j]);
                 }
             }
         }
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(ILV_NT) void interlaced_volume_kernel(const IlvArgs
         for (int tap = 0; tap < 9; ++tap) {
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                acc3 = ilv_mfma4(*reinterpret_cast<const float4*>(w3 + tap * 512 + 16 * h),
+                acc3 = mfma_k16(*reinterpret_cast<const float4*>(w3 + tap * 512 + 16 * h),
                                  *reinterpret_cast<const float4*>(A2s + ao3 + ((tap / 3) * R2W + tap % 3) * 32 + 16 * h), acc3);
         }
     }

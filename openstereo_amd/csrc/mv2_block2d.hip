@@ -28,8 +28,8 @@
 //   S = 1: 8 x 16, 4 x 8, 4 x 4        S = 2: 4 x 8, 4 x 4          x is read footprint / tile times: 1.41, 1.88, 2.25 | 1.20, 1.27
 // LDS floats: FP (Ci + 4) + FP 52 + TH TW 52 + 48 (Ci + 4) + Co 52 + FP   (FP = footprint pixels); DESIGN.md 3.4e has the table.
 //
-// Packed parameters (osa_mv2_block2d_pack_f32), Ch (Ci + Co + 13) + 2 Co floats:
-//   W1 [Ch][Ci] | s1 [Ch] | b1 [Ch] | DW [9][Ch] | s2 [Ch] | b2 [Ch] | W3 [Co][Ch] | s3 [Co] | b3 [Co]
+// Packed parameters (osa_mv2_block2d_pack_f32): the layout of mv2_common.h with T = 9; the folded-BN epilogues and the launcher's checks
+// shared with the 3-D block are there too.
 #include "mv2_common.h"
 
 namespace osa {
@@ -54,13 +54,6 @@ struct Mv2dGeo {
         return ((size_t)FP * (Ci + 4) + (size_t)(FP + NPIX) * MV2D_CKP + (size_t)MV2D_CK * (Ci + 4) + (size_t)Co * MV2D_CKP + FP) * sizeof(float);
     }
 };
-
-__device__ __forceinline__ mv2_f32x4 mv2d_mfma16(const float4 a, const float4 b, mv2_f32x4 c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c, 0, 0, 0);
-}
 
 template <int S, int TH, int TW>
 __global__ __launch_bounds__(MV2D_NT) void mv2_block2d_kernel(const Mv2dArgs p) {
@@ -98,9 +91,9 @@ __global__ __launch_bounds__(MV2D_NT) void mv2_block2d_kernel(const Mv2dArgs p) 
 
     // the projection tiles of this wave: tile t = wave + NWV i is (16 output channels mt) x (16 output pixels nt)
     const int ntiles = ((Co + 15) >> 4) * G::NTP;
-    mv2_f32x4 acc[G::PT];
+    osa_f32x4_t acc[G::PT];
 #pragma unroll
-    for (int i = 0; i < G::PT; ++i) acc[i] = mv2_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < G::PT; ++i) acc[i] = osa_f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     for (int ch0 = 0; ch0 < Ch; ch0 += CK) {
         const int ckl = min(CK, Ch - ch0), NQ = ckl >> 2;
@@ -117,18 +110,16 @@ __global__ __launch_bounds__(MV2D_NT) void mv2_block2d_kernel(const Mv2dArgs p) 
             const int mt = t / G::NTF, nt = t - mt * G::NTF;
             const float* const ap = w1s + min(mt * 16 + l16, ckl - 1) * CIP + q4;
             const float* const bp = xs + min(nt * 16 + l16, FP - 1) * CIP + q4;
-            mv2_f32x4 e = {0.f, 0.f, 0.f, 0.f};
+            osa_f32x4_t e = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 2
             for (int c = 0; c < Ci; c += 16) {
                 const bool live = c + q4 < Ci;              // Ci % 16 == 8: the last step has two quarters only
-                e = mv2d_mfma16(live ? ld4(ap + c) : zero4, live ? ld4(bp + c) : zero4, e);
+                e = mfma_k16(live ? ld4(ap + c) : zero4, live ? ld4(bp + c) : zero4, e);
             }
             const int c0 = mt * 16 + q4, q = nt * 16 + l16;
             if (c0 < ckl && q < FP) {
                 const float4 sc = ld4(s1 + ch0 + c0), sh = ld4(b1 + ch0 + c0);
-                *reinterpret_cast<float4*>(h1 + q * CKP + c0) =
-                    inb[q] ? make_float4(relu6f(fmaf(e[0], sc.x, sh.x)), relu6f(fmaf(e[1], sc.y, sh.y)), relu6f(fmaf(e[2], sc.z, sh.z)), relu6f(fmaf(e[3], sc.w, sh.w)))
-                           : zero4;
+                *reinterpret_cast<float4*>(h1 + q * CKP + c0) = inb[q] ? mv2_bn_relu6(e, sc, sh) : zero4;
             }
         }
         __syncthreads();
@@ -164,9 +155,7 @@ __global__ __launch_bounds__(MV2D_NT) void mv2_block2d_kernel(const Mv2dArgs p) 
             }
             const float4 sc = ld4(s2 + ch0 + c4), sh = ld4(b2 + ch0 + c4);
 #pragma unroll
-            for (int i = 0; i < WS; ++i)
-                *reinterpret_cast<float4*>(stage + (r * TW + ow0 + i) * CKP + c4) =
-                    make_float4(relu6f(fmaf(a[i].x, sc.x, sh.x)), relu6f(fmaf(a[i].y, sc.y, sh.y)), relu6f(fmaf(a[i].z, sc.z, sh.z)), relu6f(fmaf(a[i].w, sc.w, sh.w)));
+            for (int i = 0; i < WS; ++i) *reinterpret_cast<float4*>(stage + (r * TW + ow0 + i) * CKP + c4) = mv2_bn_relu6(a[i], sc, sh);
         }
         __syncthreads();
 
@@ -181,7 +170,7 @@ __global__ __launch_bounds__(MV2D_NT) void mv2_block2d_kernel(const Mv2dArgs p) 
 #pragma unroll
                 for (int c = 0; c < CK; c += 16) {
                     const bool live = c + q4 < ckl;         // the last chunk may be short, and 8 modulo 16
-                    acc[i] = mv2d_mfma16(live ? ld4(ap + c) : zero4, live ? ld4(bp + c) : zero4, acc[i]);
+                    acc[i] = mfma_k16(live ? ld4(ap + c) : zero4, live ? ld4(bp + c) : zero4, acc[i]);
                 }
             }
         }
@@ -196,7 +185,7 @@ __global__ __launch_bounds__(MV2D_NT) void mv2_block2d_kernel(const Mv2dArgs p) 
         const int r = px / TW, cx = px - r * TW, oy = oy0 + r, ox = ox0 + cx;
         if (px >= NPIX || oy >= p.Ho || ox >= p.Wo || c0 >= Co) continue;
         const float4 sc = ld4(s3 + c0), sh = ld4(b3 + c0);
-        float4 v = make_float4(fmaf(acc[i][0], sc.x, sh.x), fmaf(acc[i][1], sc.y, sh.y), fmaf(acc[i][2], sc.z, sh.z), fmaf(acc[i][3], sc.w, sh.w));
+        float4 v = mv2_bn(acc[i], sc, sh);
         if (p.res) {                                        // S == 1, Ci == Co: x + y, from the LDS copy of x
             const float4 xr = ld4(xs + ((r + 1) * FW + cx + 1) * CIP + c0);
             v.x = xr.x + v.x; v.y = xr.y + v.y; v.z = xr.z + v.z; v.w = xr.w + v.w;
@@ -225,12 +214,7 @@ static int mv2d_launch(Mv2dArgs a, hipStream_t st) {
     a.nTx = cdiv(a.Wo, TW); a.nTy = cdiv(a.Ho, TH);
     const long long wgs = (long long)a.B * a.nTx * a.nTy;
     OSA_REQUIRE(wgs <= 0x7fffffffLL, "mv2_block2d: grid too large");
-    static bool attr_set = false;
-    if (!attr_set) {
-        OSA_REQUIRE(hipFuncSetAttribute((const void*)mv2_block2d_kernel<S, TH, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MV2D_MAX_LDS) == hipSuccess,
-                    "mv2_block2d: 160 KiB of LDS per workgroup refused");
-        attr_set = true;
-    }
+    if (int rc = mv2_allow_lds<mv2_block2d_kernel<S, TH, TW>>("mv2_block2d", (int)MV2D_MAX_LDS)) return rc;
     hipLaunchKernelGGL((mv2_block2d_kernel<S, TH, TW>), dim3((unsigned)wgs), dim3(MV2D_NT), lds, st, a);
     OSA_LAUNCH_CHECK("mv2_block2d");
     return 0;
@@ -255,9 +239,7 @@ extern "C" int osa_mv2_block2d_f32(const float* x, const float* packed, const fl
                                    int residual, int relu, void* stream) {
     OSA_REQUIRE(x && packed && y, "mv2_block2d: NULL pointer");
     OSA_REQUIRE(B > 0 && H > 0 && W > 0, "mv2_block2d: bad dims");
-    OSA_REQUIRE(stride == 1 || stride == 2, "mv2_block2d: stride %d (supported: 1 and 2)", stride);
-    if (int rc = mv2_check_channels("mv2_block2d", Ci, Ch, Co, MV2D_MAX_CIO, MV2D_MAX_CH)) return rc;
-    OSA_REQUIRE(!residual || (stride == 1 && Ci == Co), "mv2_block2d: residual needs stride 1 and equal channels, got stride %d and %d -> %d", stride, Ci, Co);
+    if (int rc = mv2_check_block("mv2_block2d", stride, Ci, Ch, Co, residual, MV2D_MAX_CIO, MV2D_MAX_CH)) return rc;
     Mv2dArgs a{x, packed, addend, y, B, H, W, Ci, Ch, Co, (H - 1) / stride + 1, (W - 1) / stride + 1, residual ? 1 : 0, relu ? 1 : 0, 0, 0};
     const long long nx = (long long)B * H * W * Ci, ny = (long long)B * a.Ho * a.Wo * Co;
     OSA_REQUIRE(nx < (1ll << 31) && ny < (1ll << 31), "mv2_block2d: x or y has 2^31 elements or more");

@@ -23,8 +23,8 @@
 //   S = 1: Ch <= 96: 8 x 8 (146 KB at 96)   Ch <= 128: 6 x 8 (152 KB)   Ch <= 256: 4 x 4 (129 KB)
 //   S = 2: Ch <= 64: 4 x 8 (134 KB)         Ch <= 128: 4 x 4 (137 KB)   Ch <= 256: 2 x 4 (149 KB)
 //
-// Packed parameters (osa_mv2_block3d_pack_f32), Ch (Ci + Co + 31) + 2 Co floats:
-//   W1 [Ch][Ci] | s1 [Ch] | b1 [Ch] | DW [27][Ch] | s2 [Ch] | b2 [Ch] | W3 [Co][Ch] | s3 [Co] | b3 [Co]
+// Packed parameters (osa_mv2_block3d_pack_f32): the layout of mv2_common.h with T = 27; the folded-BN epilogues and the launcher's checks
+// shared with the 2-D block are there too.
 #include "mv2_common.h"
 #include <algorithm>
 
@@ -148,13 +148,8 @@ __global__ __launch_bounds__(MV2_NT) void mv2_block3d_kernel(const Mv2Args p) {
                     }
                 }
             }
-            const float4 sc = sc2, sh = sh2;
 #pragma unroll
-            for (int i = 0; i < WS; ++i) {
-                const float4 a = acc[i];
-                *reinterpret_cast<float4*>(stage + (r * TW + ow0 + i) * CHP + c4) =
-                    make_float4(relu6f(fmaf(a.x, sc.x, sh.x)), relu6f(fmaf(a.y, sc.y, sh.y)), relu6f(fmaf(a.z, sc.z, sh.z)), relu6f(fmaf(a.w, sc.w, sh.w)));
-            }
+            for (int i = 0; i < WS; ++i) *reinterpret_cast<float4*>(stage + (r * TW + ow0 + i) * CHP + c4) = mv2_bn_relu6(acc[i], sc2, sh2);
         }
     };
 
@@ -168,20 +163,16 @@ __global__ __launch_bounds__(MV2_NT) void mv2_block3d_kernel(const Mv2Args p) {
             const int co = min(mt * 16 + l16, Co - 1), px = nt * 16 + l16;
             const float* ap = W3 + (size_t)co * Ch + q4;
             const float* bp = stage + min(px, NPIX - 1) * CHP + q4;
-            mv2_f32x4 acc = {};
+            osa_f32x4_t acc = {};
 #pragma unroll 4
             for (int c = 0; c < Ch; c += 16) {
                 const bool live = c + q4 < Ch;                 // Ch % 16 == 8: the last step has two quarters only
-                const float4 a = live ? ld4(ap + c) : make_float4(0.f, 0.f, 0.f, 0.f), v = live ? ld4(bp + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, v.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, v.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, v.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, v.w, acc, 0, 0, 0);
+                acc = mfma_k16(live ? ld4(ap + c) : make_float4(0.f, 0.f, 0.f, 0.f), live ? ld4(bp + c) : make_float4(0.f, 0.f, 0.f, 0.f), acc);
             }
             const int oy = oy0 + px / TW, ox = ox0 + px % TW, c0 = mt * 16 + q4;
             if (px >= NPIX || oy >= p.Ho || ox >= p.Wo || c0 >= Co) continue;
             const float4 sc = ld4(s3 + c0), sh = ld4(b3 + c0);
-            float4 v = make_float4(fmaf(acc[0], sc.x, sh.x), fmaf(acc[1], sc.y, sh.y), fmaf(acc[2], sc.z, sh.z), fmaf(acc[3], sc.w, sh.w));
+            float4 v = mv2_bn(acc, sc, sh);
             if (p.res) {                                       // S == 1, Ci == Co
                 const float4 xr = ld4(p.x + ((((size_t)b * p.D + od) * p.H + oy) * p.W + ox) * Ci + c0);
                 v.x += xr.x; v.y += xr.y; v.z += xr.z; v.w += xr.w;
@@ -213,12 +204,7 @@ static int mv2_launch(Mv2Args a, hipStream_t st) {
     const int nch = (int)std::max<long long>(1, std::min<long long>(1024 / tiles, a.Do / 8));
     a.DCH = cdiv(a.Do, nch); a.nCh = cdiv(a.Do, a.DCH);
     OSA_REQUIRE(tiles * a.nCh <= 0x7fffffffLL, "mv2_block3d: grid too large");
-    static bool attr_set = false;
-    if (!attr_set) {
-        OSA_REQUIRE(hipFuncSetAttribute((const void*)mv2_block3d_kernel<S, TH, TW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess,
-                    "mv2_block3d: 160 KiB of LDS per workgroup refused");
-        attr_set = true;
-    }
+    if (int rc = mv2_allow_lds<mv2_block3d_kernel<S, TH, TW>>("mv2_block3d", 160 * 1024)) return rc;
     hipLaunchKernelGGL((mv2_block3d_kernel<S, TH, TW>), dim3((unsigned)(tiles * a.nCh)), dim3(MV2_NT), lds, st, a);
     OSA_LAUNCH_CHECK("mv2_block3d");
     return 0;
@@ -243,9 +229,7 @@ extern "C" int osa_mv2_block3d_f32(const float* x, const float* packed, float* y
                                    void* stream) {
     OSA_REQUIRE(x && packed && y, "mv2_block3d: NULL pointer");
     OSA_REQUIRE(B > 0 && D > 0 && H > 0 && W > 0, "mv2_block3d: bad dims");
-    OSA_REQUIRE(stride == 1 || stride == 2, "mv2_block3d: stride %d (supported: 1 and 2)", stride);
-    if (int rc = mv2_check_channels("mv2_block3d", Ci, Ch, Co, MV2_MAX_CIO, MV2_MAX_CH)) return rc;
-    OSA_REQUIRE(!residual || (stride == 1 && Ci == Co), "mv2_block3d: residual needs stride 1 and equal channels, got stride %d and %d -> %d", stride, Ci, Co);
+    if (int rc = mv2_check_block("mv2_block3d", stride, Ci, Ch, Co, residual, MV2_MAX_CIO, MV2_MAX_CH)) return rc;
     Mv2Args a{x, packed, y, B, D, H, W, Ci, Ch, Co, (D - 1) / stride + 1, (H - 1) / stride + 1, (W - 1) / stride + 1, residual ? 1 : 0, 0, 0, 0, 0};
     OSA_REQUIRE((long long)B * D * H * W * Ci < (1ll << 31) && (long long)B * a.Do * a.Ho * a.Wo * Co < (1ll << 31),
                 "mv2_block3d: x or y has 2^31 elements or more");

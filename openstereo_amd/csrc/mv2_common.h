@@ -1,5 +1,7 @@
 // What MobileStereoNet's two fused inverted-residual blocks (mv2_block3d.hip, mv2_block2d.hip) share: the packed parameter block and its
-// one small pack launch, the channel checks and the small device helpers.
+// one small pack launch, the folded-BatchNorm epilogues, the launchers' checks and their request for dynamic LDS.  The carving of the
+// block into nine pointers and the depthwise row walk stay written out in each kernel: as shared functions they changed the instruction
+// streams of the kernels (profiles/mv2_block2d/README.md).
 //
 // Packed parameters for a depthwise kernel of T taps (27 in 3-D, 9 in 2-D), Ch (Ci + Co + T + 4) + 2 Co floats:
 //   W1 [Ch][Ci] | s1 [Ch] | b1 [Ch] | DW [T][Ch] | s2 [Ch] | b2 [Ch] | W3 [Co][Ch] | s3 [Co] | b3 [Co]
@@ -8,10 +10,17 @@
 
 namespace osa {
 
-typedef float mv2_f32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ float relu6f(float v) { return fminf(fmaxf(v, 0.f), 6.f); }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+// folded BatchNorm of four channels, plain and followed by ReLU6; a: float4, or an MFMA accumulator as it is
+template <class V>
+__device__ __forceinline__ float4 mv2_bn(const V& a, const float4& sc, const float4& sh) {
+    return make_float4(fmaf(a[0], sc.x, sh.x), fmaf(a[1], sc.y, sh.y), fmaf(a[2], sc.z, sh.z), fmaf(a[3], sc.w, sh.w));
+}
+template <class V>
+__device__ __forceinline__ float4 mv2_bn_relu6(const V& a, const float4& sc, const float4& sh) {
+    return make_float4(relu6f(fmaf(a[0], sc.x, sh.x)), relu6f(fmaf(a[1], sc.y, sh.y)), relu6f(fmaf(a[2], sc.z, sh.z)), relu6f(fmaf(a[3], sc.w, sh.w)));
+}
 
 static inline size_t mv2_packed_floats(int taps, int Ci, int Ch, int Co) { return (size_t)Ch * (Ci + Co + taps + 4) + 2 * (size_t)Co; }
 
@@ -42,6 +51,26 @@ static inline int mv2_check_channels(const char* who, int Ci, int Ch, int Co, in
     OSA_REQUIRE(Ci % 8 == 0 && Ch % 8 == 0 && Co % 8 == 0, "%s: channels %d -> %d -> %d (supported: multiples of 8)", who, Ci, Ch, Co);
     OSA_REQUIRE(Ci <= max_cio && Co <= max_cio && Ch <= max_ch, "%s: channels %d -> %d -> %d (supported: input and output <= %d, hidden <= %d)",
                 who, Ci, Ch, Co, max_cio, max_ch);
+    return 0;
+}
+
+// the checks of a block launch that depend on neither rank nor tile, in the order the callers report them
+static inline int mv2_check_block(const char* who, int stride, int Ci, int Ch, int Co, int residual, int max_cio, int max_ch) {
+    OSA_REQUIRE(stride == 1 || stride == 2, "%s: stride %d (supported: 1 and 2)", who, stride);
+    if (int rc = mv2_check_channels(who, Ci, Ch, Co, max_cio, max_ch)) return rc;
+    OSA_REQUIRE(!residual || (stride == 1 && Ci == Co), "%s: residual needs stride 1 and equal channels, got stride %d and %d -> %d", who, stride, Ci, Co);
+    return 0;
+}
+
+// allow `bytes` of dynamic LDS per workgroup for KERNEL, once per process
+template <auto KERNEL>
+static int mv2_allow_lds(const char* who, int bytes) {
+    static bool done = false;
+    if (!done) {
+        OSA_REQUIRE(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess,
+                    "%s: %d KiB of LDS per workgroup refused", who, bytes / 1024);
+        done = true;
+    }
     return 0;
 }
 

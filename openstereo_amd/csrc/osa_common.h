@@ -100,6 +100,15 @@ __device__ __forceinline__ void store16(float* dst, const uint4& v) {
 #endif
 }
 
+// K = 16 of a 16 x 16 fp32 tile as four v_mfma_f32_16x16x4_f32: lane quarter q (lane >> 4) supplies elements 4q + j of the K step as one
+// float4 per operand; an fmaf chain in a fixed order (mv2_block3d.hip, mv2_block2d.hip, interlaced_volume.hip)
+__device__ __forceinline__ osa_f32x4_t mfma_k16(const float4 a, const float4 b, osa_f32x4_t c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, c, 0, 0, 0);
+}
+
 // ---- f16x3 operand splitting (conv_kernel.h arithmetic modes; shared with the volume builder's split output) ----
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));

@@ -129,41 +129,59 @@ Tensor4 mr_volume_bwd(const OptTensor& dv0, const OptTensor& dv1, const OptTenso
     return out;
 }
 
-// MobileStereoNet's 3-D inverted-residual block in eval mode (models/msnet/submodule.py:136-173; csrc/mv2_block3d.hip).  An inference op:
-// no Autograd kernel (attach keeps the reference's forward in training mode and whenever a gradient is required).
+// MobileStereoNet's fused inverted-residual blocks in eval mode (models/msnet/submodule.py:94-173; csrc/mv2_block3d.hip, csrc/mv2_block2d.hip).
+// Inference ops: no Autograd kernel (attach keeps the reference's forward in training mode and whenever a gradient is required).  The two
+// forms share the pack and the argument checks; a form is its op name, its spatial rank, its weight shapes as the message states them and
+// its packed size.
+struct Mv2Form {
+    const char* op; int rank; const char* weights;
+    size_t (*packed_floats)(int, int, int);
+};
+static constexpr Mv2Form MV2_3D{"mv2_block3d", 3, "mv2_block3d_pack: weights must be [Ch,Ci,1,1,1], [Ch,1,3,3,3] and [Co,Ch,1,1,1]", osa_mv2_block3d_packed_floats};
+static constexpr Mv2Form MV2_2D{"mv2_block2d", 2, "mv2_block2d_pack: weights must be [Ch,Ci,1,1], [Ch,1,3,3] and [Co,Ch,1,1]", osa_mv2_block2d_packed_floats};
 struct Mv2Dims { int Ci, Ch, Co; };
+template <const Mv2Form& F>
 static Mv2Dims mv2_pack_dims(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, at::TensorList bn) {
-    TORCH_CHECK(w1.dim() == 5 && wd.dim() == 5 && w3.dim() == 5 && w1.sizes().slice(2) == at::IntArrayRef({1, 1, 1}) && w3.sizes().slice(2) == at::IntArrayRef({1, 1, 1}) &&
-                wd.sizes().slice(1) == at::IntArrayRef({1, 3, 3, 3}) && wd.size(0) == w1.size(0) && w3.size(1) == w1.size(0),
-                "mv2_block3d_pack: weights must be [Ch,Ci,1,1,1], [Ch,1,3,3,3] and [Co,Ch,1,1,1]");
+    const std::vector<int64_t> ones(F.rank, 1), dw(F.rank, 3);
+    TORCH_CHECK(w1.dim() == F.rank + 2 && wd.dim() == F.rank + 2 && w3.dim() == F.rank + 2 && w1.sizes().slice(2) == at::IntArrayRef(ones) &&
+                w3.sizes().slice(2) == at::IntArrayRef(ones) && wd.size(1) == 1 && wd.sizes().slice(2) == at::IntArrayRef(dw) && wd.size(0) == w1.size(0) &&
+                w3.size(1) == w1.size(0), F.weights);
     const int64_t n[6] = {w1.size(0), w1.size(0), w1.size(0), w1.size(0), w3.size(0), w3.size(0)};
     for (int i = 0; i < 6; ++i)
-        TORCH_CHECK(bn[i].dim() == 1 && bn[i].size(0) == n[i], "mv2_block3d_pack: folded BatchNorm vector ", i, " has shape ", bn[i].sizes(), ", expected [", n[i], "]");
+        TORCH_CHECK(bn[i].dim() == 1 && bn[i].size(0) == n[i], F.op, "_pack: folded BatchNorm vector ", i, " has shape ", bn[i].sizes(), ", expected [", n[i], "]");
     return {(int)w1.size(1), (int)w1.size(0), (int)w3.size(0)};
 }
-at::Tensor mv2_block3d_pack_meta(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2,
-                                 const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
-    const Mv2Dims d = mv2_pack_dims(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
-    return at::empty({(int64_t)osa_mv2_block3d_packed_floats(d.Ci, d.Ch, d.Co)}, w1.options().dtype(at::kFloat));
+template <const Mv2Form& F>
+at::Tensor mv2_pack_meta(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2, const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
+    const Mv2Dims d = mv2_pack_dims<F>(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
+    return at::empty({(int64_t)F.packed_floats(d.Ci, d.Ch, d.Co)}, w1.options().dtype(at::kFloat));
 }
-at::Tensor mv2_block3d_pack(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2,
-                            const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
+template <const Mv2Form& F>
+at::Tensor mv2_pack(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2, const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
+    const std::string what = std::string(F.op) + "_pack argument";
     at::Tensor t[9];
     int i = 0;
-    for (const at::Tensor* s : {&w1, &wd, &w3, &s1, &b1, &s2, &b2, &s3, &b3}) t[i++] = gpu_f32(*s, "mv2_block3d_pack argument").detach().contiguous();
-    const Mv2Dims d = mv2_pack_dims(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
-    auto packed = mv2_block3d_pack_meta(w1, wd, w3, s1, b1, s2, b2, s3, b3);
-    OSA_CALL(osa_mv2_block3d_pack_f32(fp(t[0]), fp(t[1]), fp(t[2]), fp(t[3]), fp(t[4]), fp(t[5]), fp(t[6]), fp(t[7]), fp(t[8]), packed.data_ptr<float>(), d.Ci, d.Ch, d.Co, cur_stream()));
+    for (const at::Tensor* s : {&w1, &wd, &w3, &s1, &b1, &s2, &b2, &s3, &b3}) t[i++] = gpu_f32(*s, what.c_str()).detach().contiguous();
+    const Mv2Dims d = mv2_pack_dims<F>(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
+    at::Tensor packed = mv2_pack_meta<F>(w1, wd, w3, s1, b1, s2, b2, s3, b3);
+    if constexpr (F.rank == 3)
+        OSA_CALL(osa_mv2_block3d_pack_f32(fp(t[0]), fp(t[1]), fp(t[2]), fp(t[3]), fp(t[4]), fp(t[5]), fp(t[6]), fp(t[7]), fp(t[8]), packed.data_ptr<float>(), d.Ci, d.Ch, d.Co, cur_stream()));
+    else
+        OSA_CALL(osa_mv2_block2d_pack_f32(fp(t[0]), fp(t[1]), fp(t[2]), fp(t[3]), fp(t[4]), fp(t[5]), fp(t[6]), fp(t[7]), fp(t[8]), packed.data_ptr<float>(), d.Ci, d.Ch, d.Co, cur_stream()));
     return packed;
+}
+// the checks of a block call of either form; -> the output extent of an input extent
+static auto mv2_check_block(const Mv2Form& f, const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t stride, bool residual) {
+    TORCH_CHECK(x.dim() == f.rank + 2, f.op, ": x must be ", f.rank == 3 ? "[B,Ci,D,H,W]" : "[B,Ci,H,W]", ", got ", x.sizes());
+    TORCH_CHECK(stride == 1 || stride == 2, f.op, ": stride ", stride, " (supported: 1 and 2)");
+    TORCH_CHECK(Ch > 0 && Co > 0 && packed.dim() == 1 && packed.size(0) == (int64_t)f.packed_floats((int)x.size(1), (int)Ch, (int)Co),
+                f.op, ": packed parameters of ", packed.numel(), " floats do not belong to channels ", x.size(1), " -> ", Ch, " -> ", Co);
+    TORCH_CHECK(!residual || (stride == 1 && x.size(1) == Co), f.op, ": residual needs stride 1 and equal channels");
+    return [stride](int64_t n) { return (n - 1) / stride + 1; };
 }
 // -> logical [B, Co, Do, Ho, Wo] with channels_last_3d strides
 at::Tensor mv2_block3d_meta(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t stride, bool residual) {
-    TORCH_CHECK(x.dim() == 5, "mv2_block3d: x must be [B,Ci,D,H,W], got ", x.sizes());
-    TORCH_CHECK(stride == 1 || stride == 2, "mv2_block3d: stride ", stride, " (supported: 1 and 2)");
-    TORCH_CHECK(Ch > 0 && Co > 0 && packed.dim() == 1 && packed.size(0) == (int64_t)osa_mv2_block3d_packed_floats((int)x.size(1), (int)Ch, (int)Co),
-                "mv2_block3d: packed parameters of ", packed.numel(), " floats do not belong to channels ", x.size(1), " -> ", Ch, " -> ", Co);
-    TORCH_CHECK(!residual || (stride == 1 && x.size(1) == Co), "mv2_block3d: residual needs stride 1 and equal channels");
-    auto out = [&](int64_t n) { return (n - 1) / stride + 1; };
+    const auto out = mv2_check_block(MV2_3D, x, packed, Ch, Co, stride, residual);
     return mr_empty(x, x.size(0), Co, out(x.size(2)), out(x.size(3)), out(x.size(4)), true);
 }
 at::Tensor mv2_block3d(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t stride, bool residual) {
@@ -179,41 +197,9 @@ at::Tensor mv2_block3d(const at::Tensor& x, const at::Tensor& packed, int64_t Ch
     OSA_CALL(osa_mv2_block3d_f32(fp(xc), fp(packed), y.data_ptr<float>(), (int)B, (int)D, (int)H, (int)W, (int)Ci, (int)Ch, (int)Co, (int)stride, residual ? 1 : 0, cur_stream()));
     return y;
 }
-
-// MobileStereoNet's 2-D inverted-residual block in eval mode with the caller's addend and ReLU (models/msnet/submodule.py:94-133,
-// MSNet2D.py:10-45; csrc/mv2_block2d.hip).  Inference ops like mv2_block3d.
-static Mv2Dims mv2d_pack_dims(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, at::TensorList bn) {
-    TORCH_CHECK(w1.dim() == 4 && wd.dim() == 4 && w3.dim() == 4 && w1.sizes().slice(2) == at::IntArrayRef({1, 1}) && w3.sizes().slice(2) == at::IntArrayRef({1, 1}) &&
-                wd.sizes().slice(1) == at::IntArrayRef({1, 3, 3}) && wd.size(0) == w1.size(0) && w3.size(1) == w1.size(0),
-                "mv2_block2d_pack: weights must be [Ch,Ci,1,1], [Ch,1,3,3] and [Co,Ch,1,1]");
-    const int64_t n[6] = {w1.size(0), w1.size(0), w1.size(0), w1.size(0), w3.size(0), w3.size(0)};
-    for (int i = 0; i < 6; ++i)
-        TORCH_CHECK(bn[i].dim() == 1 && bn[i].size(0) == n[i], "mv2_block2d_pack: folded BatchNorm vector ", i, " has shape ", bn[i].sizes(), ", expected [", n[i], "]");
-    return {(int)w1.size(1), (int)w1.size(0), (int)w3.size(0)};
-}
-at::Tensor mv2_block2d_pack_meta(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2,
-                                 const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
-    const Mv2Dims d = mv2d_pack_dims(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
-    return at::empty({(int64_t)osa_mv2_block2d_packed_floats(d.Ci, d.Ch, d.Co)}, w1.options().dtype(at::kFloat));
-}
-at::Tensor mv2_block2d_pack(const at::Tensor& w1, const at::Tensor& wd, const at::Tensor& w3, const at::Tensor& s1, const at::Tensor& b1, const at::Tensor& s2,
-                            const at::Tensor& b2, const at::Tensor& s3, const at::Tensor& b3) {
-    at::Tensor t[9];
-    int i = 0;
-    for (const at::Tensor* s : {&w1, &wd, &w3, &s1, &b1, &s2, &b2, &s3, &b3}) t[i++] = gpu_f32(*s, "mv2_block2d_pack argument").detach().contiguous();
-    const Mv2Dims d = mv2d_pack_dims(w1, wd, w3, {s1, b1, s2, b2, s3, b3});
-    auto packed = mv2_block2d_pack_meta(w1, wd, w3, s1, b1, s2, b2, s3, b3);
-    OSA_CALL(osa_mv2_block2d_pack_f32(fp(t[0]), fp(t[1]), fp(t[2]), fp(t[3]), fp(t[4]), fp(t[5]), fp(t[6]), fp(t[7]), fp(t[8]), packed.data_ptr<float>(), d.Ci, d.Ch, d.Co, cur_stream()));
-    return packed;
-}
-// -> logical [B, Co, Ho, Wo] with channels_last strides
+// the 2-D form takes the caller's addend and ReLU (MSNet2D.py:10-45) -> logical [B, Co, Ho, Wo] with channels_last strides
 at::Tensor mv2_block2d_meta(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t stride, bool residual, const OptTensor& addend, bool) {
-    TORCH_CHECK(x.dim() == 4, "mv2_block2d: x must be [B,Ci,H,W], got ", x.sizes());
-    TORCH_CHECK(stride == 1 || stride == 2, "mv2_block2d: stride ", stride, " (supported: 1 and 2)");
-    TORCH_CHECK(Ch > 0 && Co > 0 && packed.dim() == 1 && packed.size(0) == (int64_t)osa_mv2_block2d_packed_floats((int)x.size(1), (int)Ch, (int)Co),
-                "mv2_block2d: packed parameters of ", packed.numel(), " floats do not belong to channels ", x.size(1), " -> ", Ch, " -> ", Co);
-    TORCH_CHECK(!residual || (stride == 1 && x.size(1) == Co), "mv2_block2d: residual needs stride 1 and equal channels");
-    auto out = [&](int64_t n) { return (n - 1) / stride + 1; };
+    const auto out = mv2_check_block(MV2_2D, x, packed, Ch, Co, stride, residual);
     const int64_t B = x.size(0), Ho = out(x.size(2)), Wo = out(x.size(3));
     if (addend.has_value() && addend->defined())
         TORCH_CHECK(addend->sizes() == at::IntArrayRef({B, Co, Ho, Wo}), "mv2_block2d: addend has shape ", addend->sizes(), ", expected [", B, ", ", Co, ", ", Ho, ", ", Wo, "]");
@@ -1448,9 +1434,9 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
     m.impl("gwc_volume", &gwc_volume);
     m.impl("mr_volume", &mr_volume);
     m.impl("mr_volume_bwd", &mr_volume_bwd);
-    m.impl("mv2_block3d_pack", &mv2_block3d_pack);
+    m.impl("mv2_block3d_pack", &mv2_pack<MV2_3D>);
     m.impl("mv2_block3d", &mv2_block3d);
-    m.impl("mv2_block2d_pack", &mv2_block2d_pack);
+    m.impl("mv2_block2d_pack", &mv2_pack<MV2_2D>);
     m.impl("mv2_block2d", &mv2_block2d);
     m.impl("interlaced_volume_pack", &interlaced_volume_pack);
     m.impl("interlaced_volume", &interlaced_volume);
@@ -1517,9 +1503,9 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
     m.impl("gwc_volume", &gwc_volume_meta);
     m.impl("mr_volume", &mr_volume_meta);
     m.impl("mr_volume_bwd", &mr_volume_bwd_meta);
-    m.impl("mv2_block3d_pack", &mv2_block3d_pack_meta);
+    m.impl("mv2_block3d_pack", &mv2_pack_meta<MV2_3D>);
     m.impl("mv2_block3d", &mv2_block3d_meta);
-    m.impl("mv2_block2d_pack", &mv2_block2d_pack_meta);
+    m.impl("mv2_block2d_pack", &mv2_pack_meta<MV2_2D>);
     m.impl("mv2_block2d", &mv2_block2d_meta);
     m.impl("interlaced_volume_pack", &interlaced_volume_pack_meta);
     m.impl("interlaced_volume", &interlaced_volume_meta);

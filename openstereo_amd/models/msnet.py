@@ -9,21 +9,28 @@ from .. import _ext, ops
 from ..engine import bn_scale_shift, cached_pack
 from .interlaced import interlaced_volume
 
-def mv2_block2d(blk, x, addend=None, relu=False):
-    """relu?(blk(x) (+ addend)) for a MobileV2_Residual `blk` (submodule.py:94-133: `conv` of eight entries, `use_res_connect`): one fused
-    launch where csrc/mv2_block2d.hip applies, else the block's own composition followed by the same sum and ReLU as torch operators"""
-    c, ts = blk.conv, [t for t in (x, addend) if t is not None]
-    dw = c[3] if len(c) == 8 else None                    # expanse_ratio == 1: five entries, no expansion
-    if (dw is None or blk.training or torch.is_autocast_enabled() or any(t.dim() != 4 or not t.is_cuda or t.dtype != torch.float32 for t in ts)
+def mv2_block(blk, x, addend=None, relu=False, rank=2):
+    """relu?(blk(x) (+ addend)) for a MobileV2_Residual (rank 2) or MobileV2_Residual_3D (rank 3) `blk` (submodule.py:94-173: `conv` of eight entries, `use_res_connect`): one
+    fused launch where csrc/mv2_block2d.hip / mv2_block3d.hip applies, else the block's own composition; the sum and the ReLU are the 2-D kernel's epilogue, else torch operators"""
+    c, one, ts, dw = blk.conv, (1,) * rank, [t for t in (x, addend) if t is not None], blk.conv[3] if len(blk.conv) == 8 else None   # expanse_ratio == 1: five entries, no dw
+    tops = {2: (192, 384, 192), 3: (128, 256, 128)}[rank]     # the most input, hidden and output channels csrc/mv2_block2d.hip / mv2_block3d.hip take
+    if (dw is None or blk.training or torch.is_autocast_enabled() or any(t.dim() != rank + 2 or not t.is_cuda or t.dtype != torch.float32 for t in ts)
             or (torch.is_grad_enabled() and any(t.requires_grad for t in (*ts, *c.parameters())))        # an inference op: it records no gradient
-            or (dw.kernel_size, dw.padding, dw.dilation) != ((3, 3), (1, 1), (1, 1)) or dw.stride not in ((1, 1), (2, 2))
-            or any(n % 8 or n > top for n, top in ((c[0].in_channels, 192), (dw.out_channels, 384), (c[6].out_channels, 192)))):   # the kernel's limits
+            or (dw.kernel_size, dw.padding, dw.dilation) != ((3,) * rank, one, one) or dw.stride not in (one, (2,) * rank)
+            or any(n % 8 or n > top for n, top in zip((c[0].in_channels, dw.out_channels, c[6].out_channels), tops))):
         y = x + c(x) if blk.use_res_connect else c(x)
-        y = y if addend is None else y + addend
-        return torch.relu(y) if relu else y
-    ns = _ext.load()
-    pk = cached_pack(blk, "_eng", lambda: ns.mv2_block2d_pack(c[0].weight, dw.weight, c[6].weight, *bn_scale_shift(c[1]), *bn_scale_shift(c[4]), *bn_scale_shift(c[7])))
-    return ns.mv2_block2d(x, pk, dw.out_channels, c[6].out_channels, dw.stride[0], bool(blk.use_res_connect), addend, bool(relu))
+    else:
+        ns = _ext.load()
+        pk = cached_pack(blk, "_eng", lambda: getattr(ns, f"mv2_block{rank}d_pack")(c[0].weight, dw.weight, c[6].weight, *bn_scale_shift(c[1]), *bn_scale_shift(c[4]), *bn_scale_shift(c[7])))
+        args = (x, pk, dw.out_channels, c[6].out_channels, dw.stride[0], bool(blk.use_res_connect))
+        if rank == 2:
+            return ns.mv2_block2d(*args, addend, bool(relu))
+        y = ns.mv2_block3d(*args)
+    y = y if addend is None else y + addend
+    return torch.relu(y) if relu else y
+
+
+mv2_block2d = mv2_block                                      # the name of the 2-D form (rank 2 is the default)
 
 
 def mv2_sequential(seq, x, addend=None):
@@ -50,13 +57,7 @@ class MobileV2Residual3D(torch.nn.Module):
         self._eng = None
 
     def forward(self, x):
-        c = self.conv
-        if len(c) != 8 or x.dim() != 5 or not x.is_cuda or x.dtype != torch.float32 or torch.is_autocast_enabled():
-            y = c(x)                                     # the block's own composition: expanse_ratio == 1, CPU, other dtypes, autocast
-            return x + y if self.use_res_connect else y
-        ns = _ext.load()
-        pk = cached_pack(self, "_eng", lambda: ns.mv2_block3d_pack(c[0].weight, c[3].weight, c[6].weight, *bn_scale_shift(c[1]), *bn_scale_shift(c[4]), *bn_scale_shift(c[7])))
-        return ns.mv2_block3d(x, pk, c[3].out_channels, c[6].out_channels, c[3].stride[0], bool(self.use_res_connect))
+        return mv2_block(self, x, rank=3)
 
 
 class MobileV2Residual2D(MobileV2Residual3D):                # reset_engine as above

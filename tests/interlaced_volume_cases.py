@@ -12,7 +12,7 @@ Per plane i < min(D, W) both crop the left features to x >= i and the right ones
 odd), run the three Conv3d on the one-channel volume and the 1x1 head, and write the result to V[:, :, i, :, i:]; the rest of V is zero
 (the reference fails for planes i >= W; the restatement leaves them zero).
 
-The tolerance rule (as in tests/mv2_block3d_cases.py and tests/mr_volume_cases.py): err(X) = max |X - float64 restatement| on the same
+The tolerance rule (as in tests/mv2_cases_common.py and tests/mr_volume_cases.py): err(X) = max |X - float64 restatement| on the same
 inputs, and every checked tensor X must satisfy err(X) <= 8 * err(float32 restatement).
 
 A test of this construct passes vacuously when a ReLU never clips, when relu(shift) is zero (zero padding of an intermediate could then be

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 import interlaced_volume_cases as IV
 import mv2_block2d_cases as M
+import mv2_cases_common as C
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -36,31 +37,7 @@ def gpu_block(case):
     return M.make_block(case).to(DEV)
 
 
-class Entered:
-    """counts the calls of every block's `conv` Sequential under `module`: the torch composition ran"""
-
-    def __init__(self, module, cls=M.Block):
-        self.n = 0
-        self.hooks = [m.conv.register_forward_hook(self._hit) for m in module.modules() if isinstance(m, cls)]
-        assert self.hooks
-
-    def _hit(self, *a):
-        self.n += 1
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        for h in self.hooks:
-            h.remove()
-
-
-def fused(blk, x, run=None):
-    """eval, no grad: the fused launch, proven by `conv` never being entered"""
-    with Entered(blk) as e, torch.no_grad():
-        y = blk(x) if run is None else run(blk, x)
-    assert e.n == 0, "the torch composition ran instead of the fused kernel"
-    return y
+Entered, fused = functools.partial(C.Entered, cls=M.Block), functools.partial(C.fused, cls=M.Block)
 
 
 def cl(x):
@@ -202,7 +179,7 @@ def test_whole_msnet2d_with_every_fusable_block_on_the_engine():
     only for the 3 -> 9 -> 32 block of `firstconv`, once per image (without the fused block every block of the model enters it)"""
     net = IV.make_msnet2d().to(DEV)
     L, R = (t.to(DEV) for t in IV.e2e_images())
-    with Entered(net, IV.MV2) as e, torch.no_grad():
+    with Entered(net, cls=IV.MV2) as e, torch.no_grad():
         d = net({"left": L, "right": R})["disp_pred"]
     assert e.n == 2, f"`conv` of a block was entered {e.n} times"
     want = torch.from_numpy(np.load(IV.GOLDEN)["e2e__disp_pred"])

@@ -1,7 +1,7 @@
 """GPU: MobileStereoNet's 3-D inverted-residual block as one launch (csrc/mv2_block3d.hip; osa_native.mv2_block3d; models/msnet.py grafted
 onto the restatement of tests/mv2_block3d_cases.py) by the tolerance rule stated there: every case in both memory formats, the padding of
 the HIDDEN tensor, bit-reproducibility, independence of the batch size, hipGraph capture, an hourglass3D of such blocks, and the cases in
-which the block's own torch composition runs instead."""
+which the block's own torch composition runs instead (the kernel's channel limits among them)."""
 import copy
 import functools
 
@@ -11,6 +11,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import mv2_block3d_cases as M
+import mv2_cases_common as C
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -31,31 +32,7 @@ def gpu_block(case):
     return M.make_block(case).to(DEV)
 
 
-class Entered:
-    """counts the calls of every block's `conv` Sequential under `module`: the torch composition ran"""
-
-    def __init__(self, module):
-        self.n = 0
-        self.hooks = [m.conv.register_forward_hook(self._hit) for m in module.modules() if isinstance(m, M.Block)]
-        assert self.hooks
-
-    def _hit(self, *a):
-        self.n += 1
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        for h in self.hooks:
-            h.remove()
-
-
-def fused(blk, x):
-    """eval, no grad: the fused launch, proven by `conv` never being entered"""
-    with Entered(blk) as e, torch.no_grad():
-        y = blk(x)
-    assert e.n == 0, "the torch composition ran instead of the fused kernel"
-    return y
+Entered, fused = functools.partial(C.Entered, cls=M.Block), functools.partial(C.fused, cls=M.Block)
 
 
 def cl(x):
@@ -155,3 +132,18 @@ def test_fallbacks_run_the_original_composition():
     with Entered(r1) as e, torch.no_grad():
         y = r1(x)
     assert e.n == 1 and tuple(y.shape) == tuple(x.shape)
+
+
+@pytest.mark.parametrize("channels, dilation", [(20, 1), (136, 1), (32, 2)])
+def test_blocks_the_kernel_does_not_take_run_the_original_composition(channels, dilation):
+    """channels that are no multiple of 8, channels beyond the kernel's 128 input / output channels, and a dilated depthwise layer (channels
+    the kernel takes): `conv` is entered once and the result is the ungrafted composition's, bit for bit"""
+    blk = M.Block(channels, channels, 1, 2)
+    if dilation != 1:
+        blk.conv[3] = nn.Conv3d(2 * channels, 2 * channels, 3, 1, dilation, dilation=dilation, groups=2 * channels, bias=False)
+    blk = M.seed_parameters(blk, torch.Generator().manual_seed(6000 + channels)).to(DEV).eval()
+    x = torch.randn(1, channels, 2, 3, 3, generator=torch.Generator().manual_seed(6500 + channels)).to(DEV)
+    with Entered(blk) as e, torch.no_grad():
+        y = blk(x)
+        assert e.n == 1
+        assert torch.equal(y, blk._ref_forward(x))                              # the restatement's own forward, as attach._graft keeps it
