@@ -39,6 +39,8 @@
  *                               models/msnet/submodule.py:94-133, models/msnet/MSNet2D.py:10-45
  *   osa_interlaced_volume_f32   the interlaced cost volume of MSNet2D and of StereoBase's InterlacedVolume in eval mode,
  *                               models/msnet/MSNet2D.py:143-162, stereo/modeling/cost_volume/cost_volume.py:120-169
+ *   osa_disparity_attention_f32 FoundationStereo's disparity transformer (CostVolumeDisparityAttention) in eval mode,
+ *                               models/foundationstereo/core/submodule.py:540-562, fast_foundationstereo/core/submodule.py:547-603
  *   osa_geo_lookup_mr_*_f32     the multi-range lookup of IGEV++'s GRU loop (three geometry volumes of different disparity
  *                               ranges + the correlation pyramid -> four tensors), models/igevpp/geometry.py:6-87
  */
@@ -51,7 +53,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 14
+#define OSA_ABI_VERSION 15
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -722,6 +724,25 @@ int osa_interlaced_volume_pack_f32(const float* w1, const float* w2, const float
                                    const float* shift4, float* packed, int C, int k2, int k3, int F, void* stream);
 int osa_interlaced_volume_f32(const float* featL, const float* featR, const float* packed, float* out, int B, int C, int H, int W, int D, int k2, int k3,
                               int F, void* stream);
+
+/* ---- FoundationStereo's disparity transformer (models/foundationstereo/core/submodule.py:540-562, CostVolumeDisparityAttention), ABI 15 ----
+ * Eval mode, ONE launch (csrc/disparity_attention.hip).  For every pixel of cv the L disparity planes are a sequence t [L,C]:
+ *   t = t + pe[:L], then per layer
+ *   q, k, v = t Wq^T + bq, t Wk^T + bk, t Wv^T + bv;  o = concat over nhead heads of softmax(q_h k_h^T / sqrt(C / nhead)) v_h
+ *   t = LayerNorm1(t + o Wo^T + bo);  t = LayerNorm2(t + gelu(t W1^T + b1) W2^T + b2)        erf GELU, LayerNorm eps 1e-5
+ * cv and out: fp32, layout OSA_NCDHW [B,C,L,H,W] or OSA_NDHWC [B,L,H,W,C], out in cv's layout and not overlapping it; pe [L,C] fp32, the
+ * position table's first L rows.  pe, packed and NDHWC tensors 16-byte aligned.  Exact fp32, no atomics, no workspace, bit-reproducible,
+ * the same bits in both layouts and for any batch size.  Supported: C and ff multiples of 4 and <= 32, nhead a divisor of C, 1 .. 8
+ * layers, L in 1 .. 32, any B, H, W >= 1.  Every error is reported before anything is launched.
+ * osa_disparity_attention_pack_f32: the parameters stacked over the layers in nn.Linear's [out,in] layout -- w_attn [N,4,C,C] and
+ * b_attn [N,4,C] (q, k, v, out projection), w1 [N,ff,C], b1 [N,ff], w2 [N,C,ff], b2 [N,C], ln [N,4,C] (norm1 weight, norm1 bias,
+ * norm2 weight, norm2 bias) -> `packed`, osa_disparity_attention_packed_floats(C, nhead, ff, layers) = layers * (6 * 1024 + 10 * 32)
+ * floats (every matrix and vector zero padded to 32; 0 for unsupported arguments), in one small launch. */
+size_t osa_disparity_attention_packed_floats(int C, int nhead, int ff, int layers);
+int osa_disparity_attention_pack_f32(const float* w_attn, const float* b_attn, const float* w1, const float* b1, const float* w2, const float* b2,
+                                     const float* ln, float* packed, int C, int nhead, int ff, int layers, void* stream);
+int osa_disparity_attention_f32(const float* cv, const float* pe, const float* packed, float* out, int layout, int B, int C, int L, int H, int W,
+                                int nhead, int ff, int layers, void* stream);
 
 /* ---- input pre-processing on device ------------------------- */
 /* RightTopPad(edge) + HWC->CHW + /255 + (x-mean)/std for the left and right image in one launch

@@ -71,7 +71,7 @@ SIGNATURES = {
     **dict.fromkeys(("osa_softmax_softargmin_bwd_f32", "osa_softmax_softargmin_f32", "osa_softmax_softargmin_var_f32"), (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_st])),
     **dict.fromkeys(("osa_upsample_softargmin_bwd_f32", "osa_upsample_softargmin_var_f32"), (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st])),
     "osa_amax_f32": (c_i, [c_fp, C.c_longlong, c_fp, c_st]),
-    **dict.fromkeys(("osa_upsample_softargmin_bwd_workspace_bytes", "osa_mr_volume_bwd_workspace_bytes", "osa_interlaced_volume_packed_floats"), (C.c_size_t, [c_i] * 4)),
+    **dict.fromkeys(("osa_upsample_softargmin_bwd_workspace_bytes", "osa_mr_volume_bwd_workspace_bytes", "osa_interlaced_volume_packed_floats", "osa_disparity_attention_packed_floats"), (C.c_size_t, [c_i] * 4)),
     "osa_upsample_softargmin_bwd_ws_f32": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_fp, C.c_size_t, c_st]),
     "osa_deconv3d_redir_ndhwc_f32": (c_i, [c_fp] * 5 + [c_i] * 11 + [c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_f, c_st]),
     "osa_deconv3d_redir_ndhwc_f16x3": (c_i, [c_fp] * 5 + [c_i] * 11 + [c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_f, c_i, c_f, c_f, c_rng, c_st]),
@@ -121,7 +121,8 @@ SIGNATURES = {
     **dict.fromkeys(("osa_mv2_block3d_packed_floats", "osa_mv2_block2d_packed_floats"), (C.c_size_t, [c_i] * 3)),
     **dict.fromkeys(("osa_mv2_block3d_pack_f32", "osa_mv2_block2d_pack_f32"), (c_i, [c_fp] * 10 + [c_i] * 3 + [c_st])),
     "osa_mv2_block3d_f32": (c_i, [c_fp] * 3 + [c_i] * 9 + [c_st]),
-    "osa_mv2_block2d_f32": (c_i, [c_fp] * 4 + [c_i] * 9 + [c_st]),
+    **dict.fromkeys(("osa_mv2_block2d_f32", "osa_disparity_attention_f32"), (c_i, [c_fp] * 4 + [c_i] * 9 + [c_st])),
+    "osa_disparity_attention_pack_f32": (c_i, [c_fp] * 8 + [c_i] * 4 + [c_st]),
     "osa_interlaced_volume_pack_f32": (c_i, [c_fp] * 13 + [c_i] * 4 + [c_st]),
     "osa_interlaced_volume_f32": (c_i, [c_fp] * 4 + [c_i] * 8 + [c_st]),
 }

@@ -118,34 +118,22 @@ def _targets():
     igev_concat = lambda l, r, d: build_concat_volume(l, r, d, mask_left=False)   # igev/submodule.py:216-227
     reg_keep = lambda x, maxdisp: disparity_regression(x, maxdisp, keepdim=True)
     reg_nokeep = lambda x, maxdisp: disparity_regression(x, maxdisp, keepdim=False)
-    cv = "stereo.modeling.cost_volume.cost_volume"
-    return [
-        (cv, "build_gwc_volume", build_gwc_volume), (cv, "build_concat_volume", build_concat_volume),
-        (cv, "correlation_volume", correlation_volume), (cv, "build_corr_volume", build_corr_volume),
-        # dormant variants (inference; no autograd path): engine versions fall back to the reference's own code when gradients are needed
-        (cv, "compute_volume", _dormant("compute_volume")), (cv, "build_sub_volume", _dormant("build_sub_volume")),
-        ("stereo.modeling.models.stereobase.stereobase_gru", "build_sub_volume", _dormant("build_sub_volume")),
-        ("stereo.modeling.disp_pred.disp_regression", "disparity_regression", reg_keep),
-        ("stereo.modeling.disp_refinement.disp_refinement", "context_upsample", context_upsample),
-        # names already imported into model namespaces
-        ("stereo.modeling.models.stereobase.stereobase_gru", "build_gwc_volume", build_gwc_volume),
-        ("stereo.modeling.models.stereobase.stereobase_gru", "build_concat_volume", build_concat_volume),
-        ("stereo.modeling.models.stereobase.stereobase_gru", "disparity_regression", reg_keep),
-        ("stereo.modeling.models.stereobase.stereobase_gru", "context_upsample", context_upsample),
-        ("stereo.modeling.models.stereobase.igev_blocks", "context_upsample", context_upsample),
-        ("stereo.modeling.models.lightstereo.lightstereo", "correlation_volume", correlation_volume),
-        ("stereo.modeling.models.lightstereo.lightstereo", "disparity_regression", reg_keep),
-        ("stereo.modeling.models.lightstereo.lightstereo", "context_upsample", context_upsample),
-        ("stereo.modeling.models.gwcnet.gwcnet_disp_processor", "disparity_regression", reg_nokeep),
-        ("stereo.modeling.models.psmnet.psmnet_cost_processor", "cat_fms", cat_fms),
-        ("stereo.modeling.models.psmnet.psmnet_disp_processor", "FasterSoftArgmin", ops.FasterSoftArgmin),
+    cv, sb, pp = "stereo.modeling.cost_volume.cost_volume", M + "stereobase.stereobase_gru", M + "igevpp.submodule"
+    # the drop-in of every helper name, stated once.  The dormant variants (inference; no autograd path) fall back to the reference's own code when gradients are needed
+    fns = {"build_gwc_volume": build_gwc_volume, "build_concat_volume": build_concat_volume, "correlation_volume": correlation_volume, "build_corr_volume": build_corr_volume,
+           "compute_volume": _dormant("compute_volume"), "build_sub_volume": _dormant("build_sub_volume"), "disparity_regression": reg_keep, "context_upsample": context_upsample}
+    users = [(cv, "build_gwc_volume build_concat_volume correlation_volume build_corr_volume compute_volume build_sub_volume"), (sb, "build_sub_volume"),
+             ("stereo.modeling.disp_pred.disp_regression", "disparity_regression"), ("stereo.modeling.disp_refinement.disp_refinement", "context_upsample"),
+             # names already imported into model namespaces
+             (sb, "build_gwc_volume build_concat_volume disparity_regression context_upsample"), (M + "stereobase.igev_blocks", "context_upsample"),
+             (M + "lightstereo.lightstereo", "correlation_volume disparity_regression context_upsample")]
+    igev = [(M + "igev." + mod, name, igev_concat if name == "build_concat_volume" else fns[name]) for mod in ("submodule", "igev_stereo") for name in users[4][1].split()]
+    return [(mod, name, fns[name]) for mod, names in users for name in names.split()] + [
+        (M + "gwcnet.gwcnet_disp_processor", "disparity_regression", reg_nokeep), (M + "psmnet.psmnet_cost_processor", "cat_fms", cat_fms),
+        (M + "psmnet.psmnet_disp_processor", "FasterSoftArgmin", ops.FasterSoftArgmin),
         # igevpp/submodule.py:87-97, 147-159, 177-186 (its context_upsample keeps the channel dimension)
-        (M + "igevpp.submodule", "build_gwc_volume", build_gwc_volume),
-        (M + "igevpp.submodule", "disparity_regression", lambda prob, maxdisp, interval: ops.disparity_regression(prob, maxdisp, True, interval)),
-        (M + "igevpp.submodule", "disparity_variance", ops.disparity_variance),
-        (M + "igevpp.submodule", "context_upsample", lambda disp_low, up_weights: context_upsample(disp_low, up_weights).unsqueeze(1)),
-    ] + [(M + "igev." + mod, name, fn) for mod in ("submodule", "igev_stereo") for name, fn in (
-        ("build_gwc_volume", build_gwc_volume), ("build_concat_volume", igev_concat), ("disparity_regression", reg_keep), ("context_upsample", context_upsample))]
+        (pp, "build_gwc_volume", build_gwc_volume), (pp, "disparity_regression", lambda prob, maxdisp, interval: ops.disparity_regression(prob, maxdisp, True, interval)),
+        (pp, "disparity_variance", ops.disparity_variance), (pp, "context_upsample", lambda disp_low, up_weights: context_upsample(disp_low, up_weights).unsqueeze(1))] + igev
 
 
 def stub_reference_packages(ref_root: str):
@@ -220,7 +208,7 @@ M = "stereo.modeling.models."
 
 
 def _graft_plan():
-    from .models import gwcnet as GW, psmnet as PSM, igev_style as IG, lightstereo as LS, igev_update as UP, msnet as MS
+    from .models import gwcnet as GW, psmnet as PSM, igev_style as IG, lightstereo as LS, igev_update as UP, msnet as MS, foundationstereo as FS
     fwd = ("forward", "forward_cl", "forward_train", "_pack", "reset_engine")
     gru = ("_packs", "new_level", "step", "_levels")          # per-level state buffers of the update block (igev_update.py)
     return [
@@ -245,8 +233,9 @@ def _graft_plan():
         (M + "msnet.submodule", {"MobileV2_Residual_3D": (MS.MobileV2Residual3D, ("forward", "reset_engine"), True),     # submodule.py:136-173: eval mode only
                                  "MobileV2_Residual": (MS.MobileV2Residual2D, ("forward", "reset_engine"), True)}),       # submodule.py:94-133: eval mode only
         (M + "msnet.MSNet2D", {"MSNet2D": (MS.MSNet2D, ("forward", "reset_engine"), True)}),                   # MSNet2D.py:134-212: eval mode only
-        (M + "igev.update", {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}),
-        (M + "stereobase.gru_blocks", {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}),
+        *((M + mod, {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}) for mod in ("igev.update", "stereobase.gru_blocks")),
+        *((M + mod + ".core.submodule", {"CostVolumeDisparityAttention": (FS.CostVolumeDisparityAttention, ("forward", "reset_engine"), True)})   # submodule.py:540-562: eval mode only
+          for mod in ("foundationstereo", "fast_foundationstereo")),
     ]
 
 

@@ -266,6 +266,61 @@ at::Tensor interlaced_volume(const at::Tensor& left, const at::Tensor& right, co
     return out;
 }
 
+// FoundationStereo's disparity transformer in eval mode (foundationstereo/core/submodule.py:540-562; csrc/disparity_attention.hip).  Inference ops like
+// mv2_block3d.  params: per encoder layer the weight and the bias of q_proj, k_proj, v_proj, out_proj, linear1, linear2, norm1, norm2, in that order.
+struct DaDims { int C, ff, layers; };
+static DaDims da_pack_dims(at::TensorList ps, int64_t nhead) {
+    TORCH_CHECK(!ps.empty() && ps.size() % 16 == 0 && ps[0].dim() == 2 && ps[8].dim() == 2, "disparity_attention_pack: params must hold 16 tensors per layer, the weight and "
+                "the bias of q_proj, k_proj, v_proj, out_proj, linear1, linear2, norm1 and norm2");
+    const int64_t C = ps[0].size(0), ff = ps[8].size(0), N = (int64_t)ps.size() / 16;
+    TORCH_CHECK(osa_disparity_attention_packed_floats((int)C, (int)nhead, (int)ff, (int)N) > 0, "disparity_attention_pack: d_model ", C, ", ", nhead, " heads, feed-forward width ", ff,
+                ", ", N, " layers (supported: d_model and width multiples of 4 up to 32, heads dividing d_model, 1 .. 8 layers)");
+    for (int64_t n = 0; n < N; ++n)
+        for (int i = 0; i < 8; ++i) {
+            const int64_t out = i == 4 ? ff : C, in = i == 5 ? ff : C;
+            const at::Tensor &w = ps[16 * n + 2 * i], &b = ps[16 * n + 2 * i + 1];
+            TORCH_CHECK((i < 6 ? w.sizes() == at::IntArrayRef({out, in}) : w.sizes() == at::IntArrayRef({C})) && b.sizes() == at::IntArrayRef({out}),
+                        "disparity_attention_pack: layer ", n, ", module ", i, " has weight ", w.sizes(), " and bias ", b.sizes());
+        }
+    return {(int)C, (int)ff, (int)N};
+}
+at::Tensor disparity_attention_pack_meta(at::TensorList ps, int64_t nhead) {
+    const DaDims d = da_pack_dims(ps, nhead);
+    return at::empty({(int64_t)osa_disparity_attention_packed_floats(d.C, (int)nhead, d.ff, d.layers)}, ps[0].options().dtype(at::kFloat));
+}
+at::Tensor disparity_attention_pack(at::TensorList ps, int64_t nhead) {
+    const DaDims d = da_pack_dims(ps, nhead);
+    std::vector<at::Tensor> g[7];                            // w_attn, b_attn, w1, b1, w2, b2, ln: the stacked sources of the C ABI
+    for (size_t k = 0; k < ps.size(); ++k) {
+        static constexpr int group[16] = {0, 1, 0, 1, 0, 1, 0, 1, 2, 3, 4, 5, 6, 6, 6, 6};
+        g[group[k % 16]].push_back(gpu_f32(ps[k], "disparity_attention_pack argument").detach());
+    }
+    at::Tensor s[7];
+    for (int i = 0; i < 7; ++i) s[i] = at::stack(g[i]).contiguous();
+    auto packed = disparity_attention_pack_meta(ps, nhead);
+    OSA_CALL(osa_disparity_attention_pack_f32(fp(s[0]), fp(s[1]), fp(s[2]), fp(s[3]), fp(s[4]), fp(s[5]), fp(s[6]), packed.data_ptr<float>(), d.C, (int)nhead, d.ff, d.layers, cur_stream()));
+    return packed;
+}
+// -> cv's shape in cv's memory format: dense channels_last_3d stays so, everything else is (made) contiguous
+static bool da_channels_last(const at::Tensor& cv) { return !cv.is_contiguous() && cv.is_contiguous(at::MemoryFormat::ChannelsLast3d); }
+at::Tensor disparity_attention_meta(const at::Tensor& cv, const at::Tensor& pe, const at::Tensor& packed, int64_t C, int64_t nhead, int64_t ff, int64_t layers) {
+    TORCH_CHECK(cv.dim() == 5 && cv.size(1) == C, "disparity_attention: cv must be [B,", C, ",L,H,W], got ", cv.sizes());
+    const size_t n = osa_disparity_attention_packed_floats((int)C, (int)nhead, (int)ff, (int)layers);
+    TORCH_CHECK(n > 0 && packed.dim() == 1 && packed.size(0) == (int64_t)n, "disparity_attention: packed parameters of ", packed.numel(), " floats do not belong to d_model ", C, ", ",
+                nhead, " heads, feed-forward width ", ff, ", ", layers, " layers");
+    TORCH_CHECK(pe.dim() >= 2 && pe.size(-1) == C && pe.numel() == cv.size(2) * C, "disparity_attention: pe must be [", cv.size(2), ",", C, "], got ", pe.sizes());
+    return mr_empty(cv, cv.size(0), C, cv.size(2), cv.size(3), cv.size(4), da_channels_last(cv));
+}
+at::Tensor disparity_attention(const at::Tensor& cv, const at::Tensor& pe, const at::Tensor& packed, int64_t C, int64_t nhead, int64_t ff, int64_t layers) {
+    gpu_f32(cv, "cv"); gpu_f32(pe, "pe"); gpu_f32(packed, "packed");
+    auto out = disparity_attention_meta(cv, pe, packed, C, nhead, ff, layers);
+    const bool cl = da_channels_last(cv);
+    const at::Tensor x = cl ? cv : cv.contiguous(), e = pe.contiguous();
+    OSA_CALL(osa_disparity_attention_f32(fp(x), fp(e), fp(packed), out.data_ptr<float>(), cl ? OSA_NDHWC : OSA_NCDHW, (int)cv.size(0), (int)C, (int)cv.size(2), (int)cv.size(3),
+                                         (int)cv.size(4), (int)nhead, (int)ff, (int)layers, cur_stream()));
+    return out;
+}
+
 // ---- regression heads ----------------------------------------------------------------------------------------------------------
 at::Tensor softargmin(const at::Tensor& prob) {
     gpu_f32(prob, "prob");
@@ -1363,6 +1418,8 @@ TORCH_LIBRARY(osa_native, m) {
     m.def("mv2_block2d(Tensor x, Tensor packed, int hidden, int out_channels, int stride, bool residual, Tensor? addend, bool relu) -> Tensor");
     m.def("interlaced_volume_pack(Tensor w1, Tensor w2, Tensor w3, Tensor w4, Tensor scale1, Tensor shift1, Tensor scale2, Tensor shift2, Tensor scale3, Tensor shift3, Tensor scale4, Tensor shift4) -> Tensor");
     m.def("interlaced_volume(Tensor left, Tensor right, Tensor packed, int maxdisp, int k2, int k3, int features) -> Tensor");
+    m.def("disparity_attention_pack(Tensor[] params, int nhead) -> Tensor");
+    m.def("disparity_attention(Tensor cv, Tensor pe, Tensor packed, int C, int nhead, int ff, int layers) -> Tensor");
     m.def("mr_volume_bwd(Tensor? dv0, Tensor? dv1, Tensor? dv2, Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("concat_volume(Tensor left, Tensor right, int maxdisp, bool mask_left=True) -> Tensor");
     m.def("corr_volume(Tensor left, Tensor right, int maxdisp) -> Tensor");
@@ -1440,6 +1497,8 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
     m.impl("mv2_block2d", &mv2_block2d);
     m.impl("interlaced_volume_pack", &interlaced_volume_pack);
     m.impl("interlaced_volume", &interlaced_volume);
+    m.impl("disparity_attention_pack", &disparity_attention_pack);
+    m.impl("disparity_attention", &disparity_attention);
     m.impl("concat_volume", &concat_volume);
     m.impl("corr_volume", &corr_volume);
     m.impl("softargmin", &softargmin);
@@ -1509,6 +1568,8 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
     m.impl("mv2_block2d", &mv2_block2d_meta);
     m.impl("interlaced_volume_pack", &interlaced_volume_pack_meta);
     m.impl("interlaced_volume", &interlaced_volume_meta);
+    m.impl("disparity_attention_pack", &disparity_attention_pack_meta);
+    m.impl("disparity_attention", &disparity_attention_meta);
     m.impl("concat_volume", &concat_volume_meta);
     m.impl("corr_volume", &corr_volume_meta);
     m.impl("softargmin", &softargmin_meta);

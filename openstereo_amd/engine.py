@@ -116,6 +116,12 @@ def _tensor_slots(mods):
     return out
 
 
+class PackedMirror(torch.nn.Module):
+    """A mirror whose packed form is the one cached_pack entry `_eng`."""
+    def reset_engine(self):
+        self._eng = None
+
+
 def cached_pack(owner, attr, build, mods=None):
     """Packed engine form of `owner`'s layers, rebuilt whenever a source tensor changed.
 

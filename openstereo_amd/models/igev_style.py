@@ -23,17 +23,17 @@ from ..ops import empty_cl
 
 
 # ----------------------------------------------------------------------------- StereoBase-style blocks (.block.N names)
+def conv_block(conv, cout, norm_layer, act_layer):
+    """conv (+ norm) (+ activation): the `block` Sequential of common/basic_block_2d.py and basic_block_3d.py, for every Basic* class here and in stereo_models.py"""
+    return nn.Sequential(conv, *([norm_layer(cout)] if norm_layer is not None else []), *([act_layer()] if act_layer is not None else []))
+
+
 class BasicConv2d(nn.Module):
     """common/basic_block_2d.py:6-21"""
 
     def __init__(self, cin, cout, kernel_size=3, stride=1, padding=0, bias=False, norm_layer=None, act_layer=None, **kw):
         super().__init__()
-        layers = [nn.Conv2d(cin, cout, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)]
-        if norm_layer is not None:
-            layers.append(norm_layer(cout))
-        if act_layer is not None:
-            layers.append(act_layer())
-        self.block = nn.Sequential(*layers)
+        self.block = conv_block(nn.Conv2d(cin, cout, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw), cout, norm_layer, act_layer)
 
     def forward(self, x):
         return self.block(x)
@@ -44,12 +44,7 @@ class BasicConv3d(nn.Module):
 
     def __init__(self, cin, cout, kernel_size=3, stride=1, padding=0, bias=False, norm_layer=None, act_layer=None, **kw):
         super().__init__()
-        layers = [nn.Conv3d(cin, cout, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)]
-        if norm_layer is not None:
-            layers.append(norm_layer(cout))
-        if act_layer is not None:
-            layers.append(act_layer())
-        self.block = nn.Sequential(*layers)
+        self.block = conv_block(nn.Conv3d(cin, cout, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw), cout, norm_layer, act_layer)
 
 
 class BasicDeconv3d(nn.Module):
@@ -57,12 +52,7 @@ class BasicDeconv3d(nn.Module):
 
     def __init__(self, cin, cout, kernel_size, stride=1, padding=0, bias=False, norm_layer=None, act_layer=None, **kw):
         super().__init__()
-        layers = [nn.ConvTranspose3d(cin, cout, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)]
-        if norm_layer is not None:
-            layers.append(norm_layer(cout))
-        if act_layer is not None:
-            layers.append(act_layer())
-        self.block = nn.Sequential(*layers)
+        self.block = conv_block(nn.ConvTranspose3d(cin, cout, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw), cout, norm_layer, act_layer)
 
 
 class FeatureAtt(nn.Module):

@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import _ext
-from ..engine import bn_scale_shift, cached_pack
+from ..engine import bn_scale_shift, cached_pack, PackedMirror
 from ..ops import on_engine
 from .igev_style import BasicConv2d, BasicConv3d
 
@@ -43,16 +43,13 @@ def interlaced_volume(owner, convs, bns, feat_l, feat_r, maxdisp):
     return ns.interlaced_volume(feat_l.float(), feat_r.float(), pk, maxdisp, convs[1].kernel_size[0], convs[2].kernel_size[0], convs[3].out_channels)
 
 
-class InterlacedVolume(nn.Module):
+class InterlacedVolume(PackedMirror):
     def __init__(self, num_features=8):
         super().__init__()
         self.num_features = num_features
         c3 = lambda i, o, k, s: BasicConv3d(i, o, norm_layer=nn.BatchNorm3d, act_layer=nn.ReLU, kernel_size=k, stride=s, padding=(0, 1, 1))
         self.conv3d = nn.Sequential(c3(1, 16, (8, 3, 3), (8, 1, 1)), c3(16, 32, (8, 3, 3), (8, 1, 1)), c3(32, 16, (3, 3, 3), (3, 1, 1)))
         self.volume11 = BasicConv2d(16, num_features, norm_layer=nn.BatchNorm2d, act_layer=nn.ReLU, kernel_size=1, stride=1)
-        self._eng = None
-
-    def reset_engine(self):
         self._eng = None
 
     @staticmethod

@@ -6,7 +6,7 @@ layout and have no constructors of their own.  Training keeps the reference's fo
 import torch
 
 from .. import _ext, ops
-from ..engine import bn_scale_shift, cached_pack
+from ..engine import bn_scale_shift, cached_pack, PackedMirror
 from .interlaced import interlaced_volume
 
 def mv2_block(blk, x, addend=None, relu=False, rank=2):
@@ -52,10 +52,7 @@ def hourglass2d(hg, x):
     return mv2_block2d(hg.redir1, x, hg.conv6(conv5.contiguous()), True)
 
 
-class MobileV2Residual3D(torch.nn.Module):
-    def reset_engine(self):
-        self._eng = None
-
+class MobileV2Residual3D(PackedMirror):
     def forward(self, x):
         return mv2_block(self, x, rank=3)
 
@@ -66,8 +63,7 @@ class MobileV2Residual2D(MobileV2Residual3D):                # reset_engine as a
 
 
 class MSNet2D(torch.nn.Module):
-    def reset_engine(self):
-        self._eng = None
+    reset_engine = PackedMirror.reset_engine
 
     def forward(self, data):
         L, R = data["left"], data["right"]

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..ops import on_engine
-from .igev_style import BasicConv2d, BasicConv, IGEVFeatureAtt, StereoBaseCostStage, hourglass, _pack_igev
+from .igev_style import conv_block, BasicConv2d, BasicConv, IGEVFeatureAtt, StereoBaseCostStage, hourglass, _pack_igev
 from .igev_update import BasicMultiUpdateBlock, run_refinement
 from .context_encoder import MultiBasicEncoder
 from .interlaced import InterlacedVolume
@@ -46,12 +46,7 @@ class BasicDeconv2d(nn.Module):
 
     def __init__(self, cin, cout, kernel_size, stride=1, padding=0, bias=False, norm_layer=None, act_layer=None, **kw):
         super().__init__()
-        layers = [nn.ConvTranspose2d(cin, cout, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw)]
-        if norm_layer is not None:
-            layers.append(norm_layer(cout))
-        if act_layer is not None:
-            layers.append(act_layer())
-        self.block = nn.Sequential(*layers)
+        self.block = conv_block(nn.ConvTranspose2d(cin, cout, kernel_size=kernel_size, stride=stride, padding=padding, bias=bias, **kw), cout, norm_layer, act_layer)
 
     def forward(self, x):
         return self.block(x)
