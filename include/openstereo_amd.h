@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 15
+#define OSA_ABI_VERSION 16
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -171,6 +171,12 @@ int osa_conv3d_ndhwc_f32(const float* x, const float* w_packed,
                          int dil_d, int dil_h, int dil_w,
                          const float* gate_logits, int gCs,
                          int act, float slope, void* stream);
+
+/* 1 when the osa_conv3d_ndhwc_* entry of arithmetic mode `precision` (0 f32, 1 f16x3, 2 f16) takes a layer of this geometry -- tap count,
+ * tap offsets and the LDS brick of the tile the launcher would pick -- else 0.  Host arithmetic only: no launch, no tensor, no GPU needed.
+ * Ci is rounded up to the multiple of 4 the launch requires. */
+int osa_conv3d_supported(int B, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int stride,
+                         int pad_d, int pad_h, int pad_w, int dil_d, int dil_h, int dil_w, int precision);
 
 /*
  * y = act( conv_transpose3d(x, w, stride=2, padding=pad, output_padding=opad) * scale + shift + residual )

@@ -55,6 +55,7 @@ SIGNATURES = {
     **dict.fromkeys(("osa_deconv3d_pack_f32", "osa_softargmin_bwd_f32", "osa_deconv2d_pack_f32", "osa_deconv3d_pack_f16", "osa_deconv2d_pack_f16", "osa_softargmin_f32"), (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_st])),
     **dict.fromkeys(("osa_conv3d_ndhwc_f32", "osa_conv3d_ndhwc_f16"), (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_st])),
     **dict.fromkeys(("osa_deconv3d_ndhwc_f32", "osa_deconv3d_ndhwc_f16"), (c_i, [c_fp] * 6 + [c_i] * 12 + [c_fp, c_i, c_i, c_f, c_st])),
+    "osa_conv3d_supported": (c_i, [c_i] * 17),
     "osa_conv3d_pack_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_f, c_st]),
     **dict.fromkeys(("osa_deconv3d_pack_f16x3", "osa_deconv2d_pack_f16x3"), (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_f, c_st])),
     "osa_conv3d_ndhwc_f16x3": (c_i, [c_fp] * 6 + [c_i] * 19 + [c_fp, c_i, c_i, c_f, c_f, c_rng, c_st]),

@@ -18,7 +18,6 @@ unchanged (one process per GPU).
 """
 from __future__ import annotations
 
-import math
 import os
 import threading
 
@@ -928,11 +927,13 @@ def gru_gates_q(z, qpre, bias_q, cq, h, out_dtype=None):
         return _GruGatesQ.apply(z, qpre, bias_q, cq, h, out_dtype or h.dtype)
 
 
-def _wgrad_ok(m, x):
+def _wgrad_ok(m, x, forward=False):
     """Preconditions of the backward kernels for module m on input x, checked BEFORE the forward is routed to the engine (a
     dilated 3x3 conv whose weight-gradient brick exceeds the 160 KB of LDS used to pass `_eligible` and raise inside backward()).  Only
-    consulted when a gradient can actually be asked for."""
-    if not (torch.is_grad_enabled() and (m.weight.requires_grad or x.requires_grad)):
+    consulted when a gradient can actually be asked for.  forward (`_eligible`): first the limits of the forward launch itself -- tap count, LDS
+    brick; under no_grad and for frozen layers a 9x9 kernel or a wide dilation used to pass and raise in the launch -- and of the data gradient."""
+    grad = torch.is_grad_enabled() and (m.weight.requires_grad or x.requires_grad)
+    if not (grad or forward):
         return True
     nn = torch.nn
     tr = isinstance(m, (nn.ConvTranspose2d, nn.ConvTranspose3d))
@@ -952,8 +953,11 @@ def _wgrad_ok(m, x):
         Ci, Co = m.in_channels, m.out_channels
         if st == 2 and not flat and any(v % 2 for v in sp):            # stride-2 data gradient runs as the fused transposed conv: even dims
             return False
-    if any(v <= 0 for v in out):
-        return False
+    ok, g = _lib.load().osa_conv3d_supported, (int(x.shape[0]), *k, 1, *(d[i] * (k[i] - 1) - p[i] for i in range(3)), *d, _PREC_ID[_train_precision(None)])
+    if any(v <= 0 for v in out) or (forward and not tr and not (ok(g[0], *sp, Ci, Co, *k, st, *p, *g[8:]) and (st != 1 or not (grad and x.requires_grad) or ok(g[0], *out, Co, Ci, *g[1:])))):
+        return False                                           # (the stride-1 data gradient: the same launcher on dy, roles swapped, padding dil * (k - 1) - pad)
+    if not grad:
+        return True
     need = _lib.load().osa_conv3d_wgrad_workspace_bytes(int(x.shape[0]), sp[0], sp[1], sp[2], Ci, out[0], out[1], out[2], Co,
                                                         k[0], k[1], k[2], st, p[0], p[1], p[2], d[0], d[1], d[2], 1 if tr else 0)
     return need != 0
@@ -964,7 +968,7 @@ def _eligible(m, x):
         return False
     if m.groups != 1 or getattr(m, "padding_mode", "zeros") != "zeros" or isinstance(m.padding, str):
         return False
-    return _shape_eligible(m, x) and _wgrad_ok(m, x)
+    return _shape_eligible(m, x) and _wgrad_ok(m, x, True)
 
 
 def _shape_eligible(m, x):
@@ -985,7 +989,6 @@ def _shape_eligible(m, x):
         return s == (2, 2, 2) and tuple(m.kernel_size) == (3, 3, 3) and tuple(m.padding) == (1, 1, 1) and tuple(m.dilation) == (1, 1, 1) \
             and all(d % 2 == 0 for d in x.shape[2:])
     return False
-
 
 
 # ----------------------------------------------------------------------------- fused softmax + convex up-sampling (training)

@@ -251,14 +251,9 @@ static int g_b_ring_mask = (1 << 1) | (1 << 2) | (1 << 3) | (1 << 4) | (1 << 13)
 static long long g_b_ring_launches = 0;
 static int g_b_ring_mask_value() { return g_b_ring_mask; }
 
-static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const char* what,
-                       const KernelCfg* forced = nullptr) {
-#ifdef OSA_EXPERIMENTS
-    if (!forced) {
-        const int r = launch_conv_pipe(a, stride, prec, st, what);
-        if (r != 0) return r < 0 ? r : 0;
-    }
-#endif
+// Tile configuration and LDS brick of a launch: everything launch_conv decides and checks from the layer's geometry alone.  One definition
+// for the launch and for osa_conv3d_supported, so that what the query admits is what the launcher takes.
+static int plan_conv(ConvArgs& a, int stride, int prec, const char* what, const KernelCfg* forced, const KernelCfg*& kp) {
     int ci = forced ? 0 : pick_cfg(a, stride, prec);
     if (!forced && brick_bytes(a, g_cfgs[ci]) > 160 * 1024) {
         // e.g. a stride-2 3x3x3 layer whose output depth collapses to 1: fall back to the small bricks
@@ -266,7 +261,7 @@ static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const 
         for (int f : fallback)
             if (a.CoP % g_cfgs[f].N == 0 && brick_bytes(a, g_cfgs[f]) <= 160 * 1024) { ci = f; break; }
     }
-    const KernelCfg* kp = forced ? forced : &g_cfgs[ci];
+    kp = forced ? forced : &g_cfgs[ci];
     if (!forced && (ci == 11 || ci == 14) && a.Ad == 1 && !(a.act & OSA_OUT_SPLIT)) {
         // small 2-D map on the 32- / 64-pixel tiles: still few workgroups, each alone with a long K loop -> split K inside the
         // workgroup when the chunk count allows (4 groups from 16 chunks on, 2 groups from 8)
@@ -281,8 +276,8 @@ static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const 
         if (nwg >= 192) ks = 1;
         else if (nwg >= 96 && ks == 4) ks = 2;
         if (want >= 0) ks = (want > 1 && a.nchunks % want == 0) ? want : 1;
-        if (ks == 4) kp = &g_ks_cfgs[ci == 11 ? 0 : 1];
-        else if (ks == 2) kp = &g_ks_cfgs[ci == 11 ? 2 : 3];
+        const KernelCfg* split = (ks == 4) ? &g_ks_cfgs[ci == 11 ? 0 : 1] : ((ks == 2) ? &g_ks_cfgs[ci == 11 ? 2 : 3] : nullptr);
+        if (split && brick_bytes(a, *split) * ks <= 160 * 1024) kp = split;       // (every group stages a brick of its own: wide dilated taps keep the plain tile)
     }
     const KernelCfg& k = *kp;
     a.tilesD = cdiv(a.Ad, k.TD); a.tilesH = cdiv(a.Ah, k.TH); a.tilesW = cdiv(a.Aw, k.TW);
@@ -291,6 +286,21 @@ static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const 
     finish_geometry(a, k.TW, k.TW == 8 && a.isw == 1);
     const size_t brick = (size_t)a.LD * a.PlaneQ * sizeof(float4);
     OSA_REQUIRE(brick <= 160 * 1024, "%s: LDS brick %dx%dx%d needs %zu B (> 160 KiB)", what, a.LD, a.LH, a.LW, brick);
+    return 0;
+}
+
+static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const char* what,
+                       const KernelCfg* forced = nullptr) {
+#ifdef OSA_EXPERIMENTS
+    if (!forced) {
+        const int r = launch_conv_pipe(a, stride, prec, st, what);
+        if (r != 0) return r < 0 ? r : 0;
+    }
+#endif
+    const KernelCfg* kp = nullptr;
+    if (plan_conv(a, stride, prec, what, forced, kp)) return -1;
+    const KernelCfg& k = *kp;
+    const size_t brick = (size_t)a.LD * a.PlaneQ * sizeof(float4);
     // several channel chunks per staging pass (fewer barriers, more loads in flight) while the
     // workgroup stays under ~40 KiB of LDS, i.e. as long as it does not cost residency
     a.cps = 1;
@@ -872,6 +882,39 @@ static int f16_units(ConvArgs& a, const char* what) {
     return 0;
 }
 
+// Dims, output size and tap offsets of a plain convolution, with the limits they have to respect (tap count, offsets that fit the
+// kernel's signed bytes, a non-empty output).  `a` arrives zeroed.
+static int conv3d_geometry(ConvArgs& a, int B, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int stride,
+                           int pad_d, int pad_h, int pad_w, int dil_d, int dil_h, int dil_w) {
+    OSA_REQUIRE(kd >= 1 && kh >= 1 && kw >= 1, "conv3d: bad kernel %dx%dx%d", kd, kh, kw);
+    const long long T = (long long)kd * kh * kw;
+    OSA_REQUIRE(T <= MAX_TAPS, "conv3d: %dx%dx%d kernel unsupported", kd, kh, kw);
+    OSA_REQUIRE(stride == 1 || stride == 2, "conv3d: stride %d unsupported", stride);
+    OSA_REQUIRE(dil_d >= 1 && dil_h >= 1 && dil_w >= 1, "conv3d: bad dilation");
+    const int kk[3] = {kd, kh, kw}, pp[3] = {pad_d, pad_h, pad_w}, dd[3] = {dil_d, dil_h, dil_w};
+    for (int i = 0; i < 3; ++i)
+        OSA_REQUIRE(-pp[i] >= -127 && (long long)(kk[i] - 1) * dd[i] - pp[i] <= 127, "conv3d: tap offsets of axis %d leave [-127, 127]", i);
+    a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Ci = Ci;
+    a.isd = (Di == 1 && kd == 1) ? 1 : stride; a.ish = stride; a.isw = stride;
+    a.Do = (Di + 2 * pad_d - dil_d * (kd - 1) - 1) / a.isd + 1;
+    a.Ho = (Hi + 2 * pad_h - dil_h * (kh - 1) - 1) / a.ish + 1;
+    a.Wo = (Wi + 2 * pad_w - dil_w * (kw - 1) - 1) / a.isw + 1;
+    OSA_REQUIRE(Di + 2 * pad_d - dil_d * (kd - 1) - 1 >= 0 && Hi + 2 * pad_h - dil_h * (kh - 1) - 1 >= 0 && Wi + 2 * pad_w - dil_w * (kw - 1) - 1 >= 0,
+                "conv3d: empty output");
+    a.Co = Co;
+    a.Ad = a.Do; a.Ah = a.Ho; a.Aw = a.Wo;
+    a.os = 1; a.ood = a.ooh = a.oow = 0;
+    a.T = (int)T;
+    int t = 0;
+    for (int z = 0; z < kd; ++z) for (int yy = 0; yy < kh; ++yy) for (int xx = 0; xx < kw; ++xx, ++t) {
+        a.td[t] = (signed char)(z * dil_d - pad_d);
+        a.th[t] = (signed char)(yy * dil_h - pad_h);
+        a.tw[t] = (signed char)(xx * dil_w - pad_w);
+    }
+    a.nchunks = nchunks_of(Ci); a.CoP = pad32(Co);
+    return 0;
+}
+
 static int conv3d_impl(const float* x, const float* w_packed,
                        const float* scale, const float* shift, const float* residual,
                        float* y,
@@ -885,31 +928,12 @@ static int conv3d_impl(const float* x, const float* w_packed,
                        const osa_f16x3_ranges* rng = nullptr) {
     if (gate_logits) OSA_REQUIRE(gCs >= Co, "conv3d: gate stride %d < Co %d", gCs, Co);
     if (check_common("conv3d", x, w_packed, y, B, Di, Hi, Wi, Ci, xCs, Co, yCs, rCs, residual)) return -1;
-    const int T = kd * kh * kw;
-    OSA_REQUIRE(T >= 1 && T <= MAX_TAPS, "conv3d: %dx%dx%d kernel unsupported", kd, kh, kw);
-    OSA_REQUIRE(stride == 1 || stride == 2, "conv3d: stride %d unsupported", stride);
-    OSA_REQUIRE(dil_d >= 1 && dil_h >= 1 && dil_w >= 1, "conv3d: bad dilation");
     ConvArgs a;
     memset(&a, 0, sizeof(a));
+    if (conv3d_geometry(a, B, Di, Hi, Wi, Ci, Co, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w)) return -1;
     a.x = x; a.w = reinterpret_cast<const float4*>(w_packed); a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
     a.gate = gate_logits; a.gCs = gCs;
-    a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.Ci = Ci; a.xCs = xCs;
-    a.isd = (Di == 1 && kd == 1) ? 1 : stride; a.ish = stride; a.isw = stride;
-    a.Do = (Di + 2 * pad_d - dil_d * (kd - 1) - 1) / a.isd + 1;
-    a.Ho = (Hi + 2 * pad_h - dil_h * (kh - 1) - 1) / a.ish + 1;
-    a.Wo = (Wi + 2 * pad_w - dil_w * (kw - 1) - 1) / a.isw + 1;
-    OSA_REQUIRE(a.Do > 0 && a.Ho > 0 && a.Wo > 0, "conv3d: empty output");
-    a.Co = Co; a.yCs = yCs; a.rCs = rCs;
-    a.Ad = a.Do; a.Ah = a.Ho; a.Aw = a.Wo;
-    a.os = 1; a.ood = a.ooh = a.oow = 0;
-    a.T = T;
-    int t = 0;
-    for (int z = 0; z < kd; ++z) for (int yy = 0; yy < kh; ++yy) for (int xx = 0; xx < kw; ++xx, ++t) {
-        a.td[t] = (signed char)(z * dil_d - pad_d);
-        a.th[t] = (signed char)(yy * dil_h - pad_h);
-        a.tw[t] = (signed char)(xx * dil_w - pad_w);
-    }
-    a.nchunks = nchunks_of(Ci); a.CoP = pad32(Co);
+    a.xCs = xCs; a.yCs = yCs; a.rCs = rCs;
     a.act = act; a.slope = slope; a.oscale = oscale;
     if (prec == PREC_F16 && f16_units(a, "conv3d")) return -1;
     set_ranges(a, rng);
@@ -925,6 +949,19 @@ static int conv3d_impl(const float* x, const float* w_packed,
         if (r != 0) return r < 0 ? r : 0;
     }
     return launch_conv(a, stride, prec, (hipStream_t)stream, "conv3d");
+}
+
+// Would conv3d_impl take this layer?  Its own geometry checks and the launcher's plan, nothing launched and no tensor touched.
+extern "C" int osa_conv3d_supported(int B, int Di, int Hi, int Wi, int Ci, int Co, int kd, int kh, int kw, int stride,
+                                    int pad_d, int pad_h, int pad_w, int dil_d, int dil_h, int dil_w, int precision) {
+    if (B <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Ci <= 0 || Co <= 0 || precision < 0 || precision > 2) return 0;
+    const int prec = precision == 0 ? PREC_F32 : (precision == 1 ? PREC_F16X3 : PREC_F16);
+    ConvArgs a;
+    memset(&a, 0, sizeof(a));
+    if (conv3d_geometry(a, B, Di, Hi, Wi, (Ci + 3) / 4 * 4, Co, kd, kh, kw, stride, pad_d, pad_h, pad_w, dil_d, dil_h, dil_w)) return 0;
+    if (prec == PREC_F16) a.nchunks = cdiv(a.Ci, 32);
+    const KernelCfg* kp = nullptr;
+    return plan_conv(a, stride, prec, "conv3d", nullptr, kp) == 0 ? 1 : 0;
 }
 
 #define OSA_CONV_PARAMS                                                                         \
