@@ -110,7 +110,7 @@ SIGNATURES = {
     "osa_channel_sums_multi": (c_i, [c_fp, c_i, c_i, c_i, c_ll, c_i, c_fp, c_fp, C.c_size_t, c_st]),
     "osa_channel_sums": (c_i, [c_fp, c_i, c_i, c_fp, c_i, c_i, c_fp, c_fp, c_fp, c_i, c_ll, c_i, c_fp, c_fp, C.c_size_t, c_st]),
     **dict.fromkeys(("osa_conv3d_march_launches", "osa_conv3d_march_s2_launches", "osa_deconv3d_walk_launches", "osa_conv_b_ring_launches", "osa_volume_walk_launches"), (c_ll, [])),
-    **dict.fromkeys(("osa_deconv_walk", "osa_deconv_walk_segment_planes", "osa_conv_b_ring_mask", "osa_volume_walk_step"), (c_i, [c_i])),
+    **dict.fromkeys(("osa_deconv_walk", "osa_deconv_walk_segment_planes", "osa_conv_march_s2_segment_planes", "osa_conv_b_ring_mask", "osa_volume_walk_step"), (c_i, [c_i])),
     "osa_build_volume_nhwc_split_eligible": (c_i, [c_fp, c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
     "osa_build_volume_nhwc_split_f16x3": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_fp, c_fp, c_i, c_i, c_fp] + [c_i] * 7 + [c_fp, c_fp, c_fp, c_st]),
     "osa_upsample_softargmin_f32": (c_i, [c_fp, c_fp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_st]),

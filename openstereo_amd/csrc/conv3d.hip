@@ -235,7 +235,6 @@ int launch_conv_march_s2(ConvArgs& a, hipStream_t st, const char* what);
 // output-plane-walking form of the fused transposed convolutions (conv_deconv_walk.h, launched from conv_march.hip; osa_deconv_walk switches it)
 int launch_conv_deconv_walk(ConvArgs& a, hipStream_t st, const char* what);
 void wgrad_set_multi_tile(int on);   // bit 27 of the mask: the multi-tile form of the f16x3 / f16 weight gradient (csrc/wgrad.hip wgrad_mt_kernel); 0 = single-tile kernel
-void march_s2_set_waves(int w);     // bit 28 of the mask: the 4-wave 2 x 32 column (two workgroups per CU) instead of the 8-wave 4 x 32 column (one per CU)
 
 // Which tile configurations take their B operands through the LDS ring (osa_conv_b_ring_mask; bit i = conv_cfgs.def entry i, bit 30 = the
 // fused transposed convs).  Default = the tiles where the ring measured ahead at 8 AND at 4 pairs per launch (profiles/round4/
@@ -1239,5 +1238,5 @@ extern "C" int osa_debug_trace_read(unsigned long long* dst, size_t n_words) {
 }
 #endif
 
-extern "C" int osa_conv_b_ring_mask(int mask) { const int prev = osa::g_b_ring_mask; osa::g_b_ring_mask = mask; osa::march_s2_set_waves(((mask >> 28) & 1) ? 4 : 8); osa::wgrad_set_multi_tile((mask >> 27) & 1); return prev; }
+extern "C" int osa_conv_b_ring_mask(int mask) { const int prev = osa::g_b_ring_mask; osa::g_b_ring_mask = mask; osa::wgrad_set_multi_tile((mask >> 27) & 1); return prev; }
 extern "C" long long osa_conv_b_ring_launches(void) { return osa::g_b_ring_launches; }

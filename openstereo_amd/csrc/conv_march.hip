@@ -98,39 +98,10 @@ int launch_conv_march(ConvArgs& a, hipStream_t st, const char* what) {
 static long long g_march_s2_launches = 0;
 long long march_s2_launches() { return g_march_s2_launches; }
 
-static int g_march_s2_waves = 8;                            // 8: 4 x 32 columns, one workgroup per CU (measured ahead: profiles/round6/march_s2_versions.txt); 4: 2 x 32 columns, two per CU (osa_conv_b_ring_mask bit 28)
-template <int NWV>
-static int launch_conv_march_s2_t(ConvArgs& a, hipStream_t st, const char* what) {
-    using G = MarchS2Geo<NWV>;
-    a.tilesD = 1; a.tilesH = cdiv(a.Ho, G::TH); a.tilesW = cdiv(a.Wo, G::TW);
-    a.dbg = exp_int("OSA_DBG", 0);
-    // D segments of `oseg` output planes: a segment stages 2 oseg + 1 input planes (the first one for a third of its taps).  Cost model in
-    // plane-steps per round of resident workgroups; the fewest segments win a tie.
-    const long long cols = (long long)a.B * a.tilesH * a.tilesW;
-    const long long slots = 256 * (NWV == 8 ? 1 : 2);
-    int nseg = 1;
-    {
-        double best = 1e30;
-        for (int n = 1; n <= a.Do; ++n) {
-            const int os = cdiv(a.Do, n), ns = cdiv(a.Do, os);
-            if (ns != n) continue;
-            const double cost = (double)((cols * ns + slots - 1) / slots) * (2.0 * os + (ns > 1 ? 1.0 : 0.0) + 0.5);     // (+ 0.5: prologue / drain of a workgroup)
-            if (cost < best - 1e-9) { best = cost; nseg = ns; }
-        }
-        const int o = exp_int("OSA_MARCH_NSEG", 0);
-        if (o > 0 && o <= a.Do) nseg = o;
-    }
-    const int oseg = cdiv(a.Do, nseg);
-    nseg = cdiv(a.Do, oseg);
-    OSA_REQUIRE(cols * nseg < (1ll << 31), "%s: grid too large", what);
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv_march_s2_kernel<NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes()); attr_set = true; }
-    hipLaunchKernelGGL(conv_march_s2_kernel<NWV>, dim3((unsigned)(cols * nseg)), dim3(NWV * 64), G::lds_bytes(), st, a, oseg, nseg);
-    OSA_LAUNCH_CHECK(what);
-    return 1;
-}
-
-void march_s2_set_waves(int w) { g_march_s2_waves = (w == 4) ? 4 : 8; }
+// osa_conv_march_s2_segment_planes: output planes per segment, 0 = the launcher's cost model (the shipped state).  A debug setter, for the
+// segment-length ablation and for the tests, which pin segments that start on an odd plane and ragged last segments on small shapes.
+static int g_march_s2_planes = 0;
+int march_s2_planes_set(int planes) { const int prev = g_march_s2_planes; g_march_s2_planes = planes > 0 ? planes : 0; return prev; }
 
 int launch_conv_march_s2(ConvArgs& a, hipStream_t st, const char* what) {
     if (a.T != 27 || a.Co != 64 || a.CoP != 64 || a.Di < 2 || a.gate || a.rx || a.res) return 0;
@@ -141,9 +112,37 @@ int launch_conv_march_s2(ConvArgs& a, hipStream_t st, const char* what) {
     if ((a.yCs % 16) || ((size_t)a.y & 15) || ((size_t)a.x & 15)) return 0;
     if ((long long)a.Do * a.Ho * a.Wo * a.yCs >= (1ll << 31)) return 0;
     if ((long long)a.Hi * a.Wi * a.xCs >= (1ll << 29)) return 0;        // per-plane byte offsets are 32-bit
-    const int r = g_march_s2_waves == 8 ? launch_conv_march_s2_t<8>(a, st, what) : launch_conv_march_s2_t<4>(a, st, what);
-    if (r == 1) ++g_march_s2_launches;
-    return r;
+    using G = MarchS2Geo;
+    a.tilesD = 1; a.tilesH = cdiv(a.Ho, G::TH); a.tilesW = cdiv(a.Wo, G::TW);
+    // D segments of `oseg` output planes.  Cost model in sub-passes (one kd of one plane: 27 MFMAs per wave) per round of resident
+    // workgroups: an output plane takes three, a segment that does not start at plane 0 one more (kd = 0 of the odd plane in front of it);
+    // the fewest segments win a tie.
+    const long long cols = (long long)a.B * a.tilesH * a.tilesW;
+    const long long slots = 256;
+    int nseg = 1;
+    {
+        double best = 1e30;
+        for (int n = 1; n <= a.Do; ++n) {
+            const int os = cdiv(a.Do, n), ns = cdiv(a.Do, os);
+            if (ns != n) continue;
+            const double cost = (double)((cols * ns + slots - 1) / slots) * (3.0 * os + (ns > 1 ? 1.0 : 0.0) + 1.5);     // (+ 1.5: prologue / drain of a workgroup)
+            if (cost < best - 1e-9) { best = cost; nseg = ns; }
+        }
+    }
+    int oseg = cdiv(a.Do, nseg);
+    if (g_march_s2_planes > 0) oseg = g_march_s2_planes < a.Do ? g_march_s2_planes : a.Do;
+    nseg = cdiv(a.Do, oseg);
+    OSA_REQUIRE(cols * nseg < (1ll << 31), "%s: grid too large", what);
+    static bool attr_set = false;                           // once per process (not inside a graph capture of a later launch)
+    if (!attr_set) {
+        OSA_REQUIRE(hipFuncSetAttribute((const void*)conv_march_s2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes()) == hipSuccess,
+                    "%s: %d bytes of LDS per workgroup refused", what, (int)G::lds_bytes());
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(conv_march_s2_kernel, dim3((unsigned)(cols * nseg)), dim3(G::NWV * 64), G::lds_bytes(), st, a, oseg, nseg);
+    OSA_LAUNCH_CHECK(what);
+    ++g_march_s2_launches;
+    return 1;
 }
 
 // ------------------------------------------------------------------ output-plane-walking transposed form (conv_deconv_walk.h) --
@@ -222,6 +221,7 @@ int launch_conv_deconv_walk(ConvArgs& a, hipStream_t st, const char* what) {
 
 extern "C" long long osa_conv3d_march_launches(void) { return osa::march_launches(); }
 extern "C" long long osa_conv3d_march_s2_launches(void) { return osa::march_s2_launches(); }
+extern "C" int osa_conv_march_s2_segment_planes(int planes) { return osa::march_s2_planes_set(planes); }
 extern "C" long long osa_deconv3d_walk_launches(void) { return osa::deconv_walk_launches(); }
 extern "C" int osa_deconv_walk(int enable) { return osa::deconv_walk_set(enable); }
 extern "C" int osa_deconv_walk_segment_planes(int planes) { return osa::deconv_walk_planes_set(planes); }

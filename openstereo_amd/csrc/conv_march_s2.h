@@ -12,39 +12,38 @@
 //     voxels for every kw (even, odd, even + 1) -- the de-interleave costs nothing, it is the per-lane source address of the transfer.
 //     Voxels are 64 B apart (no padding slot); the 16-byte quad index is XOR-swizzled with bits 2-3 of the voxel index, which makes any
 //     16 consecutive voxels conflict-free for ds_read_b128 (4 v + (q ^ (v >> 2 & 3)) mod 16 is a bijection of v mod 16);
-//   * 8 waves = 4 M-tiles (output rows) x 2 N-tiles (32 output channels each), ONE workgroup per CU: the weights of a step are fetched once
-//     per CU into a 3-slot LDS ring (a step = one (chunk, kh, kd): 3 kw taps x [hi | lo] x 2 N-tiles = 12 KB, 9 MFMAs per wave, 18 per
-//     SIMD between barriers); the plane of pass q + 1 lands in the second plane buffer while pass q computes.
-// r6 measured [MI355X], 9 pairs per launch: HBM traffic 2.37 GB = 1.05x the algorithmic bytes (brick form: 4.89 GB = 2.16x), 1.02 ms against
-// the brick form's 1.10 ms on the same box; the default bench line (three sub-batch streams) gains 0.9 %.  Four restructured versions
-// (static 3-step blocks with software-pipelined fragment reads, triple-buffered planes with role-split loader waves, weights by ordinary
-// loads instead of LDS-DMA: tools/experiments/conv_march_s2_v5.h) cut the instructions per step from ~290 to ~65 and did NOT run faster
-// (1.13-1.16 ms): with ONE 8-wave workgroup per CU in barrier lockstep and 9 MFMAs per wave and step, a step takes ~2100 cycles whatever
-// moves the bytes -- 43 % of the wave cycles issue instructions (25 non-MFMA instructions per MFMA by the SQ counters), 31 % wait at
-// barriers / counters, LDS bank conflicts 1.7 %.  What would change it is more MFMAs per barrier (a second M-tile per wave needs plane
-// buffers this LDS cannot hold twice) or two independent workgroups per CU.  profiles/round6/march_s2_versions.txt has every line.
+//   * 8 waves = 4 M-tiles (output rows) x 2 N-tiles (32 output channels each), ONE workgroup per CU.  The unit between two barriers is a
+//     SUB-PASS (plane, chunk, kd) with all 9 (kh, kw) taps: 27 MFMAs per wave, 54 per SIMD.  An even plane is one sub-pass (kd = 1), an odd
+//     plane two (kd = 2 into the plane it completes, then kd = 0 into the next one).  The 9 taps of a (chunk, kd) are ONE contiguous 36 KB
+//     slab of the packed weights (9 taps x [hi | lo] x 2 k-groups x 64 channels x 16 B); it is copied as it lies, once per CU, into one
+//     of two LDS slab buffers: the slab of sub-pass s + 1 lands while sub-pass s multiplies, and the plane of pass q + 1 lands in the
+//     second plane buffer while pass q computes.  A fragments are read one tap ahead of the MFMAs that use them.
+// r6 (a barrier per (chunk, kh, kd), 9 MFMAs per wave between barriers, 3-slot ring of 12 KB): HBM traffic 2.37 GB = 1.05x the algorithmic
+// bytes (brick form: 4.89 GB = 2.16x), 1.02 ms at 9 pairs per launch against the brick form's 1.10 ms; a step took ~2100 cycles whatever
+// moved the bytes (profiles/round6/march_s2_versions.txt: barrier, fragment reads, address arithmetic -- 0.62 of 0.97 ms without any
+// transfer or MFMA).  This form pays that skeleton once per 27 MFMAs instead of once per 9: profiles/round8/march_s2_steps.md.
 // Same split arithmetic (Ahi.Blo + Alo.Bhi + Ahi.Bhi, fp32 accumulate), operand ranges and epilogue semantics as conv_mfma_kernel; the
-// summation order differs (plane-major), so results agree with the brick form to fp32 rounding, not bitwise.
+// summation order differs (plane-major: plane, chunk, kh, kw per output plane), so results agree with the brick form to fp32 rounding,
+// not bitwise.
 #pragma once
 #include "conv_kernel.h"
 
 namespace osa {
 
-// NWV = 8: a 4 x 32 output column, ONE workgroup per CU (112 KB of LDS); NWV = 4: a 2 x 32 column, TWO independent workgroups per CU (2 x 80 KB:
-// while one sits at its step barrier the other multiplies) at the price of a taller halo (1.27x instead of 1.14x) and the weights fetched twice per CU.
-template <int NWV_>
 struct MarchS2Geo {
-    static constexpr int NWV = NWV_, TW = 32, TH = NWV_ / 2;
+    static constexpr int NWV = 8, TW = 32, TH = 4;                             // a 4 x 32 output column, one workgroup per CU
     static constexpr int LH = 2 * TH + 1, LW = 2 * TW + 1, NEV = TW + 1;       // footprint rows / columns, even columns per row
     static constexpr int NVOX = LH * LW;                                       // 585 voxels, 4 quads each
     static constexpr int NPI = (NVOX * 4 + 63) / 64;                           // LDS-DMA instructions per chunk-plane (37)
     static constexpr int PLANEQ = NPI * 64;                                    // float4 slots per plane buffer
-    static constexpr int NP = (NPI + NWV - 1) / NWV;                           // pieces per wave and pass (5)
-    static constexpr int BRING = 3, BSTEPQ = 12 * 64;                          // ring slots, float4 slots per step (12 fragments of 1 KB)
-    static constexpr int NIB = NWV == 8 ? 2 : 3;                               // B transfers per wave and step (8 waves: 16 issued for 12 fragments, 4 duplicates)
-    static constexpr size_t lds_bytes() { return (size_t)2 * PLANEQ * 16 + (size_t)BRING * BSTEPQ * 16; }
+    static constexpr int NP = (NPI + NWV - 1) / NWV;                           // plane pieces per wave and pass (5)
+    static constexpr int NBI = 9 * 4;                                          // LDS-DMA instructions per weight slab: (tap, hi | lo, k-group) x 64 channels
+    static constexpr int BSLABQ = NBI * 64;                                    // float4 slots per slab buffer (36,864 B)
+    static constexpr int NIB = (NBI + NWV - 1) / NWV;                          // slab pieces per wave and sub-pass (5: 40 issued for 36, 4 duplicates)
+    static constexpr size_t lds_bytes() { return (size_t)2 * PLANEQ * 16 + (size_t)2 * BSLABQ * 16; }    // 149,504 B
     static_assert((size_t)NWV * 32 * 36 * 4 <= (size_t)PLANEQ * 16, "epilogue tiles must fit into one plane buffer");
 };
+static_assert(MarchS2Geo::lds_bytes() <= 160 * 1024, "one workgroup must fit into the LDS of a CU");
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt_c() {
@@ -62,12 +61,11 @@ __device__ __forceinline__ void wait_vmcnt_c() {
 }
 
 // split input, split output, no residual (conv1 of the hourglasses); oseg output planes per segment
-template <int NWV_>
-__global__ __launch_bounds__(NWV_ * 64, 2) void conv_march_s2_kernel(const ConvArgs p, const int oseg, const int nseg) {
-    using G = MarchS2Geo<NWV_>;
-    constexpr int PLANEQ = G::PLANEQ, NP = G::NP, NPI = G::NPI, NWV = G::NWV, NIB = G::NIB, TH = G::TH, TW = G::TW, LW = G::LW, NEV = G::NEV;
+__global__ __launch_bounds__(MarchS2Geo::NWV * 64, 1) void conv_march_s2_kernel(const ConvArgs p, const int oseg, const int nseg) {
+    using G = MarchS2Geo;
+    constexpr int PLANEQ = G::PLANEQ, NP = G::NP, NPI = G::NPI, NWV = G::NWV, NIB = G::NIB, NBI = G::NBI, BSLABQ = G::BSLABQ, TH = G::TH, TW = G::TW, LW = G::LW, NEV = G::NEV;
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
-    float4* const bring = smem + 2 * PLANEQ;
+    float4* const bslab = smem + 2 * PLANEQ;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -108,24 +106,20 @@ __global__ __launch_bounds__(NWV_ * 64, 2) void conv_march_s2_kernel(const ConvA
     // ---- LDS-DMA (conv_march.h: every instruction is issued by every wave with all lanes on; the vmcnt immediates count instructions)
     auto dma = [&](const char* src, const unsigned lds_byte) { lds_dma16(src, lds_byte); };
     const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-    const unsigned bring_lds = smem_lds + 2u * PLANEQ * 16u;
+    const unsigned bslab_lds = smem_lds + 2u * PLANEQ * 16u;
     const char* const zsrc = reinterpret_cast<const char*>(g_lds_dma_zeros);
 
-    // B: a step's 12 fragments f = (kw * 2 + hl) * 2 + n, 64 lanes x 16 B each.  Wave w fetches fragment w and fragment 8 + (w & 3)
-    // (waves 4..7 repeat 8..11: the same bytes to the same slots, so that every wave issues exactly NIB instructions per step).
-    // packed weights: 16-byte unit ((ch * 27 + t) * 4 + hl * 2 + kg) * CoP + co, t = kd * 9 + kh * 3 + kw  (conv3d.hip pack_weights_f16x3)
-    unsigned boff[NIB], bdst[NIB];
+    // B: the slab of a (chunk, kd) is the packed weights as they lie -- 16-byte unit ((ch * 27 + t) * 4 + hl * 2 + kg) * CoP + co, t = kd * 9 +
+    // kh * 3 + kw (conv3d.hip pack_weights_f16x3) -- 36 instructions of 64 units.  Piece i of this wave is instruction i * NWV + wave (beyond
+    // NBI - 1: instruction NBI - 1 again, the same bytes to the same slots, so that every wave issues exactly NIB instructions per sub-pass).
+    auto dma_b = [&](const int buf, const int ch, const int kd) {
+        const char* base = reinterpret_cast<const char*>(p.w) + (size_t)((ch * 27 + kd * 9) * 4 * CoP) * 16 + lane * 16;
 #pragma unroll
-    for (int i = 0; i < NIB; ++i) {
-        const int f = NWV == 8 ? (i == 0 ? wv : 8 + (wv & 3)) : wv * 3 + i;
-        const int kw = f >> 2, hl = (f >> 1) & 1, n = f & 1;
-        boff[i] = (unsigned)((kw * 4 * CoP + hl * 2 * CoP + hh * CoP + n * 32 + col) * 16);
-        bdst[i] = (unsigned)(f * 64 * 16);
-    }
-    auto dma_b = [&](const int slot, const int ch, const int kh, const int kd) {
-        const char* base = reinterpret_cast<const char*>(p.w) + (size_t)((ch * 27 + kd * 9 + kh * 3) * 4 * CoP) * 16;
-#pragma unroll
-        for (int i = 0; i < NIB; ++i) dma(base + boff[i], bring_lds + (unsigned)(slot * G::BSTEPQ * 16) + bdst[i]);
+        for (int i = 0; i < NIB; ++i) {
+            int n = i * NWV + wv;
+            n = n < NBI ? n : NBI - 1;
+            dma(base + n * 1024, bslab_lds + (unsigned)((buf * BSLABQ + n * 64) * 16));
+        }
     };
 
     // planes: piece i of this wave is DMA instruction n = i * NWV + wave (beyond NPI - 1: instruction NPI - 1 again).  LDS slot j = 64 n + lane
@@ -147,14 +141,13 @@ __global__ __launch_bounds__(NWV_ * 64, 2) void conv_march_s2_kernel(const ConvA
     }
     const size_t plane_bytes = (size_t)p.Hi * p.Wi * p.xCs * 4;
     const char* const xb = reinterpret_cast<const char*>(p.x) + (size_t)b * p.Di * plane_bytes;
-    auto dma_plane = [&](const int buf, const int pd, const int c) {          // pd < 0: nothing to fetch (zeros: the instruction count stays the same)
-        const char* base = xb + (size_t)(pd < 0 ? 0 : pd) * plane_bytes + (size_t)c * (CC * 4);
+    auto dma_plane = [&](const int buf, const int pd, const int c) {
+        const char* base = xb + (size_t)pd * plane_bytes + (size_t)c * (CC * 4);
 #pragma unroll
         for (int i = 0; i < NP; ++i) {
             int n = i * NWV + wv;
             n = n < NPI ? n : NPI - 1;
-            const bool ok = ((pvalid >> i) & 1u) && pd >= 0;
-            dma(ok ? base + poff[i] : zsrc, smem_lds + (unsigned)((buf * PLANEQ + n * 64) * 16));
+            dma(((pvalid >> i) & 1u) ? base + poff[i] : zsrc, smem_lds + (unsigned)((buf * PLANEQ + n * 64) * 16));
         }
     };
 
@@ -197,78 +190,83 @@ __global__ __launch_bounds__(NWV_ * 64, 2) void conv_march_s2_kernel(const ConvA
         }
     };
 
-    // ---- one step: the 3 kw taps of (kh, kd) from plane buffer `cur`, B fragments from ring slot `slot`, 9 MFMAs
-    auto taps = [&](f32x16& acc, const int cur, const int slot, const int kh) {
-        const int vrow = (2 * wm + kh) * LW + col;
-        float4 A[3][2], Bf[3][2];
+    // ---- one sub-pass: the 9 (kh, kw) taps of one kd from plane buffer `cur`, B fragments from slab buffer `wb`, 27 MFMAs in the order kh, kw,
+    // split term.  aq[t]: float4 slot of this lane's hi quad of tap t in a plane buffer (the lo quad is slot ^ 2); the fragments of tap t + 1
+    // are read into the other register set before the MFMAs of tap t.
+    int aq[9];
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw) {
-            const int v = vrow + (kw == 1 ? NEV : (kw >> 1));
-            const int qs = hh ^ ((v >> 2) & 3);
-            A[kw][0] = smem[cur * PLANEQ + 4 * v + qs];
-            A[kw][1] = smem[cur * PLANEQ + 4 * v + (qs ^ 2)];
-            Bf[kw][0] = bring[slot * G::BSTEPQ + ((kw * 2 + 0) * 2 + wn) * 64 + lane];
-            Bf[kw][1] = bring[slot * G::BSTEPQ + ((kw * 2 + 1) * 2 + wn) * 64 + lane];
-        }
+    for (int t = 0; t < 9; ++t) {
+        const int kh = t / 3, kw = t % 3;
+        const int v = (2 * wm + kh) * LW + col + (kw == 1 ? NEV : (kw >> 1));
+        aq[t] = 4 * v + (hh ^ ((v >> 2) & 3));
+    }
+    const int bq = hh * 64 + wn * 32 + col;                   // this lane's unit inside a (tap, hi | lo) pair of k-group rows
+    auto taps = [&](f32x16& acc, const int cur, const int wb) {
+        const float4* const pa = smem + cur * PLANEQ;
+        const float4* const pb = bslab + wb * BSLABQ + bq;
+        float4 A[2][2], Bf[2][2];
+        A[0][0] = pa[aq[0]]; A[0][1] = pa[aq[0] ^ 2];
+        Bf[0][0] = pb[0]; Bf[0][1] = pb[2 * 64];
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw)
+        for (int t = 0; t < 9; ++t) {
+            const int s = t & 1;
+            if (t + 1 < 9) {
+                A[s ^ 1][0] = pa[aq[t + 1]]; A[s ^ 1][1] = pa[aq[t + 1] ^ 2];
+                Bf[s ^ 1][0] = pb[((t + 1) * 4 + 0) * 64]; Bf[s ^ 1][1] = pb[((t + 1) * 4 + 2) * 64];
+            }
 #pragma unroll
             for (int term = 0; term < 3; ++term) {                      // small cross terms first (as the other forms)
-                const f16x8 a = __builtin_bit_cast(f16x8, A[kw][term == 1 ? 1 : 0]);
-                const f16x8 w = __builtin_bit_cast(f16x8, Bf[kw][term == 0 ? 1 : 0]);
+                const f16x8 a = __builtin_bit_cast(f16x8, A[s][term == 1 ? 1 : 0]);
+                const f16x8 w = __builtin_bit_cast(f16x8, Bf[s][term == 0 ? 1 : 0]);
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, w, acc, 0, 0, 0);
             }
+        }
     };
 
-    // ---- pass / step sequence.  Planes pf .. pl are walked; pass = (plane pd, chunk c); an even plane has 3 steps (kh, kd = 1), an odd plane
-    // 3 steps (kh, kd = 2) into the plane od = pd >> 1 it completes (if that plane belongs to this segment) + 3 steps (kh, kd = 0) into od + 1
-    // (if that one does).  Global step t uses ring slot t % 3.
+    // ---- pass / sub-pass sequence.  Planes pf .. pl are walked; pass = (plane pd, chunk c); an even plane has one sub-pass (kd = 1), an odd
+    // plane one (kd = 2) into the plane od = pd >> 1 it completes (if that plane belongs to this segment) + one (kd = 0) into od + 1 (if that
+    // one does).  Global sub-pass s uses slab buffer s & 1.
     const int pf = (2 * o0 - 1 > 0) ? 2 * o0 - 1 : 0;
     const int pl = (2 * o1 - 1 < p.Di - 1) ? 2 * o1 - 1 : p.Di - 1;
-    auto steps_of = [&](const int pd) { const int od = pd >> 1; return (pd & 1) ? ((od >= o0 ? 3 : 0) + (od + 1 < o1 ? 3 : 0)) : 3; };
-    auto kd_of = [&](const int pd, const int k) { return (pd & 1) ? ((k < 3 && (pd >> 1) >= o0) ? 2 : 0) : 1; };
-    // look-ahead iterator of the B transfers (two steps ahead of the step being computed); past the end it stays on the last step
-    int lpd = pf, lc = 0, lk = 0;
-    bool ldone = false;
-    auto issue_b = [&](const int slot) {
-        dma_b(slot, lc, lk >= 3 ? lk - 3 : lk, kd_of(lpd, lk));
-        if (!ldone) {
-            if (++lk == steps_of(lpd)) {
-                lk = 0;
-                if (++lc == nch) { lc = 0; ++lpd; }
-                if (lpd > pl) { ldone = true; lpd = pl; lc = nch - 1; lk = steps_of(pl) - 1; }
-            }
+    auto subs_of = [&](const int pd) { const int od = pd >> 1; return (pd & 1) ? ((od >= o0 ? 1 : 0) + (od + 1 < o1 ? 1 : 0)) : 1; };
+    auto kd_of = [&](const int pd, const int j) { return (pd & 1) ? ((j == 0 && (pd >> 1) >= o0) ? 2 : 0) : 1; };
+    // look-ahead iterator of the slab transfers (one sub-pass ahead of the one being computed); lpd > pl: no sub-pass follows
+    int lpd = pf, lc = 0, lj = 0;
+    auto issue_b = [&](const int buf) {
+        dma_b(buf, lc, kd_of(lpd, lj));
+        if (++lj == subs_of(lpd)) {
+            lj = 0;
+            if (++lc == nch) { lc = 0; ++lpd; }
         }
     };
 
     dma_plane(0, pf, 0);
-    issue_b(0); issue_b(1);
+    issue_b(0);
     wait_vmcnt_c<0>();
 
-    int slot = 0;                                             // ring slot of the step being computed
+    int wb = 0;                                               // slab buffer of the sub-pass being computed
     int q = 0;
     for (int pd = pf; pd <= pl; ++pd) {
         const bool odd = pd & 1;
         const int od = pd >> 1;
         const bool do0 = !odd || od >= o0;
-        const int ns = steps_of(pd);
+        const int ns = subs_of(pd);
         for (int c = 0; c < nch; ++c, ++q) {
             const int cur = q & 1;
             // plane-chunk of pass q + 1
             int npd = pd, nc = c + 1;
             if (nc == nch) { nc = 0; ++npd; }
-            if (npd > pl) npd = -1;
-            for (int k = 0; k < ns; ++k) {
-                __syncthreads();                                  // every wave's share of this step's B (and, at k = 0, of this pass's plane) has landed;
-                                                                  // the previous step's readers of ring slot (slot + 2) % 3 are done
-                issue_b(slot >= 1 ? slot - 1 : 2);                // step t + 2 -> slot (t + 2) % 3
-                if (k == 0) dma_plane(cur ^ 1, npd, nc);
-                const int kh = k >= 3 ? k - 3 : k;
-                if (odd && !(k < 3 && do0)) taps(acc1, cur, slot, kh);
-                else taps(acc0, cur, slot, kh);
-                // B of step t + 1 is home (issued a step ago); younger: this step's B transfer and -- during steps 0 and 1 -- the plane pieces
-                if (k <= 1) wait_vmcnt_c<NIB + NP>(); else wait_vmcnt_c<NIB>();
-                slot = slot == 2 ? 0 : slot + 1;
+            for (int j = 0; j < ns; ++j) {
+                __syncthreads();                                  // every wave's share of this sub-pass's slab (and, at j = 0, of this pass's plane) has landed;
+                                                                  // the previous sub-pass's readers of slab buffer wb ^ 1 (at j = 0: of plane buffer cur ^ 1) are done
+                if (lpd <= pl) issue_b(wb ^ 1);                   // slab of sub-pass s + 1
+                const bool stage = j == 0 && npd <= pl;
+                if (stage) dma_plane(cur ^ 1, npd, nc);
+                if (odd && !(j == 0 && do0)) taps(acc1, cur, wb);
+                else taps(acc0, cur, wb);
+                // the next sub-pass's slab must be home; while this pass goes on, the plane pieces (issued AFTER the slab) may stay in flight
+                if (stage && j + 1 < ns) wait_vmcnt_c<NP>(); else wait_vmcnt_c<0>();
+                wb ^= 1;
             }
             if (c + 1 == nch) {                                   // plane pd complete: does an output plane complete with it?
                 const bool fin = odd || pd == p.Di - 1;           // (an even LAST plane: plane pd + 1 lies outside the tensor)
@@ -284,7 +282,6 @@ __global__ __launch_bounds__(NWV_ * 64, 2) void conv_march_s2_kernel(const ConvA
             }
         }
     }
-    wait_vmcnt_c<0>();                                            // (the zero pieces / spare B transfers of the last pass)
     if (p.out_meta) {
         __syncthreads();
         publish_amax(p.out_meta, am, amax_seen, reinterpret_cast<float*>(smem));
