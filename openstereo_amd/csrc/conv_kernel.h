@@ -1022,13 +1022,15 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
                 continue;
             }
             if (vok[k] && cok && !(p.dbg & 32)) {             // dbg 32: no stores (timing only)
-                am = fmaxf(am, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
                 float* yp = yb + (v0[k] + coff) * p.yCs + co;
-                if (vec4) store16(yp, make_float4(o[0], o[1], o[2], o[3]));
-                else {
+                if (vec4) {
+                    am = fmaxf(am, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
+                    store16(yp, make_float4(o[0], o[1], o[2], o[3]));
+                } else {
+                    // only stored lanes count: a padded lane of a ragged quad holds act(0), 0.5 under a sigmoid (and 0.25 more under a sigmoid gate)
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        if (co + e < p.Co) yp[e] = o[e];
+                        if (co + e < p.Co) { am = fmaxf(am, fabsf(o[e])); yp[e] = o[e]; }
                 }
             }
         }

@@ -77,7 +77,9 @@ def test_stride2_marching_conv_vs_torch_and_brick(case, lib):
         torch.testing.assert_close(got, back(yb)[:, :Co].cpu(), atol=3e-5, rtol=3e-5, msg=lambda m: f"stride-2 marching conv [{name}] vs brick form: {m}")
         # the range block of the output (max |value| of what was written) must cover the tensor: the next layer scales by it
         from openstereo_amd import ranges
-        assert float(ranges.amax_of(ranges.meta_of(y))) >= float(ref.abs().max()) * (1 - 1e-5)
+        import range_block_cases as R
+        R.check_recorded_max(float(ranges.amax_of(ranges.meta_of(y))), R.decode_split(y, ranges.meta_of(y).cpu()), "split", name)
+        assert float(ranges.amax_of(ranges.meta_of(y))) >= float(ref.abs().max()) * (1 - 1e-5)      # (and it covers the reference's maximum, as before)
 
 
 def test_layers_outside_the_form_keep_the_brick_kernel(lib):
