@@ -1,5 +1,5 @@
-// 3-D cost-aggregation convolutions for gfx950: host side (tile selection, LDS geometry, weight packing, C ABI) and the
-// instantiations of the stage -> barrier -> taps kernel.  Kernel template: conv_kernel.h.
+// 3-D cost-aggregation convolutions for gfx950: host side (tile selection, LDS geometry, weight packing, C ABI).
+// Kernel template: conv_kernel.h; its instantiations: conv_inst_<mode>.hip.
 #include "conv_kernel.h"
 #include "conv_inst.h"
 
@@ -131,102 +131,6 @@ static size_t brick_bytes(ConvArgs& a, const KernelCfg& k) {
     return (size_t)a.LD * a.LH * (a.LW * VS + 64) * sizeof(float);   // upper bound incl. row padding
 }
 
-#ifdef OSA_EXPERIMENTS
-// conv_pipe.hip -- experiments build only (tools/build_variant.sh, OSA_PIPE=1): measured slower than the form below on every
-// layer it covers (profiles/round2/pipe_ablation.txt), so the shipped library neither links nor selects it.
-void (*pipe_kernel(int tile, int ring, int outs))(const ConvArgs);
-
-// Persistent LDS-DMA pipelined launch (conv_kernel.h, PIPE = 1) for the layers it covers: f16x3, split input, unit
-// stride, no gate, output channels filling one N tile of 32 / 64 / 128.  Returns 1 when launched, 0 when not eligible.
-static int launch_conv_pipe(ConvArgs& a, int stride, int prec, hipStream_t st, const char* what) {
-    if (prec != PREC_F16X3 || !(a.act & OSA_IN_SPLIT) || stride != 1 || a.isd != 1 || a.ish != 1 || a.isw != 1) return 0;
-    if (a.gate || a.rx || a.os != 1 || a.Ci % CC != 0 || !exp_int("OSA_PIPE", 0)) return 0;
-    if (a.Ad < 2) return 0;                            // flat (2-D) maps: the 3-D bricks below would idle 3 of their 4 planes
-    const int tile = (a.CoP == 32) ? 0 : ((a.CoP == 64) ? 1 : ((a.CoP == 128) ? 2 : -1));
-    if (tile < 0) return 0;
-    static const KernelCfg shapes[3] = { {"pipe_2x1_4x1_8x8", 256, 32, 4, 8, 8, 256, 0, 3, -1},
-                                         {"pipe_2x2_4x1_8x8", 256, 64, 4, 8, 8, 256, 0, 3, -1},
-                                         {"pipe_2x2_2x2_8x8", 128, 128, 2, 8, 8, 256, 0, 3, -1} };
-    const KernelCfg& k = shapes[tile];
-    if ((long long)a.Di * a.Hi * a.Wi * a.xCs * 4 >= (1ll << 32)) return 0;          // per-row buffer descriptors: 32-bit byte counts
-    a.tilesD = cdiv(a.Ad, k.TD); a.tilesH = cdiv(a.Ah, k.TH); a.tilesW = cdiv(a.Aw, k.TW);
-    (void)brick_bytes(a, k);
-    if (a.LW * 4 > 64 || (long long)a.LD * a.LH * a.LW >= 65536) return 0;          // one LDS-DMA instruction per brick row
-    finish_geometry(a, k.TW, true);
-    if (a.VQ != 4) return 0;
-    const size_t brick = (size_t)a.LD * a.PlaneQ * sizeof(float4);
-    const size_t epi = (size_t)(k.threads / 64) * 32 * 36 * sizeof(float);
-    if (brick < epi || 2 * brick > 80 * 1024) return 0;                              // epilogue tiles live in one buffer; 2 workgroups per CU
-    a.cps = 1; a.dma = 1;
-    const long long nitems = (long long)a.B * a.tilesD * a.tilesH * a.tilesW;
-    if (nitems >= (1ll << 31)) return 0;
-    if (a.act & OSA_OUT_SPLIT) {
-        OSA_REQUIRE(a.Co % 16 == 0 && a.yCs % 16 == 0 && ((size_t)a.y & 15) == 0, "%s: split output needs Co, yCs %% 16 == 0", what);
-        if (a.res) OSA_REQUIRE(a.act & OSA_RES_SPLIT, "%s: a split output takes a split residual", what);
-    }
-    if ((a.act & OSA_RES_SPLIT) && a.res) OSA_REQUIRE(a.Co % 16 == 0 && a.rCs % 16 == 0 && ((size_t)a.res & 15) == 0,
-                                                      "%s: split residual needs Co, rCs %% 16 == 0", what);
-    {
-        const long long ovox = (long long)a.Do * a.Ho * a.Wo;
-        const int cs = a.yCs > a.rCs ? a.yCs : a.rCs;
-        OSA_REQUIRE(ovox * cs < (1ll << 31), "%s: one batch item of the output exceeds 2^31 elements", what);
-    }
-    void (*fn)(const ConvArgs) = pipe_kernel(tile, a.T % 3 == 0, (a.act & OSA_OUT_SPLIT) != 0);
-    if (!fn) return 0;
-    const int lds = (int)(2 * brick);
-    static bool attr_set[3][2][2];
-    bool& done = attr_set[tile][a.T % 3 == 0][(a.act & OSA_OUT_SPLIT) != 0];
-    if (!done) { (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds); done = true; }
-    const int resident = exp_int("OSA_PIPE_WGS", 2) * 256;                           // 2 workgroups per CU x 256 CUs
-    a.dbg = exp_int("OSA_DBG", 0);
-    const unsigned grid = (unsigned)(nitems < resident ? nitems : resident);
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(k.threads + 64), lds, st, a);         // + the loader wave
-    OSA_LAUNCH_CHECK(what);
-    return 1;
-}
-
-#endif   // OSA_EXPERIMENTS
-
-// Start-up stagger of the first dispatch wave (conv_kernel.h).  slots = workgroups that share a CU (LDS and wave limits), period =
-// what one workgroup lasts when it has the CU to itself in every phase -- modelled from the launch geometry, not measured:
-//   taps   : MFMAs per wave x 32 (f16x3: 3 per product, 8 passes x 4 cycles) or x 64 (f32: 32x32x2, 16 passes) cycles
-//   memory : bytes the workgroup moves (staged brick x chunks + output tile + residual) at its share of ~4 TB/s
-// Slot s starts s * period / slots late.  Launches that do not fill the chip twice over gain nothing and are left alone.
-static int resident_workgroups(void (*fn)(const ConvArgs), int threads, size_t lds) {
-    // what the hardware will co-schedule on one CU (registers, LDS, wave slots), memoised per (kernel, LDS size)
-    struct Key { const void* f; size_t l; int n; };
-    static Key cache[64]; static int used = 0;
-    for (int i = 0; i < used; ++i) if (cache[i].f == (const void*)fn && cache[i].l == lds) return cache[i].n;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fn, threads, lds) != hipSuccess) { (void)hipGetLastError(); n = 1; }
-    if (used < 64) cache[used++] = Key{(const void*)fn, lds, n};
-    return n;
-}
-
-static void set_stagger(ConvArgs& a, const KernelCfg& k, void (*fn)(const ConvArgs), size_t lds, long long nwg, bool deconv, int prec) {
-    a.stag_ticks = 0; a.stag_n = 0; a.stag_cus = 256;
-    const int mode = exp_int("OSA_STAG", 0);      // measured neutral (profiles/round3/stagger_sweep_B8.txt): experiments build only
-    if (!mode) return;
-    const int waves = k.threads / 64;
-    int slots = resident_workgroups(fn, k.threads, lds);
-    { const int o = exp_int("OSA_STAG_K", 0); if (o) slots = o; }
-    if (slots < 2 || nwg < (long long)2 * slots * 256) return;
-    // period model (cycles at ~2 GHz -> 10 ns ticks)
-    const double mfma_per_wave = (double)a.nchunks * a.T * ((double)k.M * k.N / 1024.0 / waves) * (prec == PREC_F16X3 ? 3.0 : 8.0);
-    const double tap_us = mfma_per_wave * (prec == PREC_F16X3 ? 32.0 : 64.0) / 2000.0;
-    const double bytes = (double)a.LD * a.LH * a.LW * 64.0 * a.nchunks + (double)k.M * (deconv ? 8 : 1) * k.N * 4.0 * (a.res || a.rx ? 2 : 1);
-    const double mem_us = bytes / (4.0e6 / 256.0);         // 4 TB/s over 256 CUs = 15.6 KB/us per CU
-    // de-phased steady state: the CU's matrix pipes need slots * tap_us per round of its workgroups, its memory share slots * mem_us,
-    // and a single workgroup cannot finish faster than tap_us + mem_us  ->  consecutive slots start max(...) / slots apart
-    double step_us = tap_us > mem_us ? tap_us : mem_us;
-    if ((tap_us + mem_us) / slots > step_us) step_us = (tap_us + mem_us) / slots;
-    { const int o = exp_int("OSA_STAG_PCT", 100); step_us *= o / 100.0; }
-    { const int o = exp_int("OSA_STAG_US10", 0); if (o) step_us = o / 10.0; }
-    a.stag_ticks = (int)(step_us * 100.0 + 0.5);
-    a.stag_n = slots * 256; a.stag_cus = 256;
-    if (exp_int("OSA_STAG_PRINT", 0)) fprintf(stderr, "[stagger] %s slots %d tap %.2f us mem %.2f us step %.2f us\n", k.name, slots, tap_us, mem_us, step_us);
-}
-
 // d-marching form of the 3x3x3 stride-1 32-output-channel layers (f16x3): conv_march.hip.  1 = launched, 0 = not eligible, -1 = error
 int launch_conv_march(ConvArgs& a, hipStream_t st, const char* what);
 // d-marching form of the 3x3x3 stride-2 64-output-channel layers (f16x3, split tensors): conv_march.hip / conv_march_s2.h.  Switch: bit 29 of
@@ -290,12 +194,6 @@ static int plan_conv(ConvArgs& a, int stride, int prec, const char* what, const 
 
 static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const char* what,
                        const KernelCfg* forced = nullptr) {
-#ifdef OSA_EXPERIMENTS
-    if (!forced) {
-        const int r = launch_conv_pipe(a, stride, prec, st, what);
-        if (r != 0) return r < 0 ? r : 0;
-    }
-#endif
     const KernelCfg* kp = nullptr;
     if (plan_conv(a, stride, prec, what, forced, kp)) return -1;
     const KernelCfg& k = *kp;
@@ -315,9 +213,6 @@ static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const 
         lds = brick * k.ks;
         if (lds < red) lds = red;
     }
-#ifndef OSA_TB
-#define OSA_TB 1
-#endif
     const size_t epi = (size_t)(k.threads / 64) * OSA_TB * 32 * 36 * sizeof(float);   // wave-private transpose tiles of the epilogue
     if (lds < epi) lds = epi;
     { const size_t m = (size_t)exp_int("OSA_LDS_MIN", 0); if (m > lds) lds = m; }   // experiments: cap residency
@@ -358,9 +253,9 @@ static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const 
     void (*fn)(const ConvArgs) = (kf.fn3 && a.T % 3 == 0 && !no_ring) ? kf.fn3 : kf.fn;
     if (a.act & OSA_OUT_SPLIT) {
         fn = (kf.fns3 && a.T % 3 == 0 && !no_ring) ? kf.fns3 : kf.fns;
-        OSA_REQUIRE(fn != nullptr || kf.fnbs != nullptr, "%s: this tile configuration has no split- / fp16-output variant", what);
+        OSA_REQUIRE(fn != nullptr, "%s: this tile configuration has no split- / fp16-output variant", what);
     }
-    OSA_REQUIRE(fn != nullptr || kf.fnb != nullptr, "%s: tile configuration %s is not built for this arithmetic mode", what, k.name);
+    OSA_REQUIRE(fn != nullptr, "%s: tile configuration %s is not built for this arithmetic mode", what, k.name);
     // B operands through the LDS ring (conv_kernel.h, BL = 1; f16x3 / f16 modes): a 4-slot ring of one tap step's fragments
     // (2 KB per 32 output channels of the workgroup) above the bricks and the epilogue tiles.  Bit-identical results.
     a.ringQ = 0;
@@ -368,14 +263,12 @@ static int launch_conv(ConvArgs& a, int stride, int prec, hipStream_t st, const 
         void (*fb)(const ConvArgs) = (a.act & OSA_OUT_SPLIT) ? kf.fnbs : kf.fnb;
         const size_t ring = (size_t)4 * 2 * (k.N / 32) * 1024;
         const int bit = (k.table == 0) ? (int)(&k - g_cfgs) : 30;     // osa_conv_b_ring_mask: conv_cfgs.def index, 30 = the fused transposed convs
-        const bool use = fb != nullptr && k.ks <= 1 && (((g_b_ring_mask >> bit) & 1) || fn == nullptr) && lds + ring <= 160 * 1024;   // (fn == nullptr: a ring-only tile)
+        const bool use = fb != nullptr && k.ks <= 1 && ((g_b_ring_mask >> bit) & 1) && lds + ring <= 160 * 1024;
         if (use) { fn = fb; a.ringQ = (int)(lds / 16); lds += ring; ++g_b_ring_launches; }
-        OSA_REQUIRE(fn != nullptr, "%s: tile configuration %s exists in the ring form only and its ring does not fit", what, k.name);
     }
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 grid((unsigned)nblk, a.CoP / k.N), block(k.threads);
-    set_stagger(a, k, fn, lds, (long long)grid.x * grid.y, forced != nullptr, prec);
     hipLaunchKernelGGL(fn, grid, block, lds, st, a);
     OSA_LAUNCH_CHECK(what);
     return 0;
@@ -1224,19 +1117,6 @@ static int small_co_impl(const float* x, const float* w_ref, bool packed, const 
     OSA_LAUNCH_CHECK("conv3d_small_co");
     return 0;
 }
-
-#ifdef OSA_TRACE_ON
-// -DOSA_TRACE_ON builds only: copy the in-kernel timeline (conv_kernel.h, OSA_DBG & 256) to the host and clear it
-extern "C" int osa_debug_trace_read(unsigned long long* dst, size_t n_words) {
-    const size_t have = (size_t)osa::TRACE_SLOTS * osa::TRACE_WAVES * osa::TRACE_EVENTS;
-    if (n_words > have) n_words = have;
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(osa::g_trace), n_words * sizeof(unsigned long long)) != hipSuccess) return -1;
-    static unsigned long long zeros[osa::TRACE_SLOTS * osa::TRACE_WAVES * osa::TRACE_EVENTS];
-    if (hipMemcpyToSymbol(HIP_SYMBOL(osa::g_trace), zeros, sizeof(zeros)) != hipSuccess) return -1;
-    return (int)n_words;
-}
-#endif
 
 extern "C" int osa_conv_b_ring_mask(int mask) { const int prev = osa::g_b_ring_mask; osa::g_b_ring_mask = mask; osa::wgrad_set_multi_tile((mask >> 27) & 1); return prev; }
 extern "C" long long osa_conv_b_ring_launches(void) { return osa::g_b_ring_launches; }

@@ -18,8 +18,8 @@
 //                     taps that hit real (non-inserted) inputs -> no zero insertion, no wasted MACs
 // Epilogue (fused): folded eval-mode BatchNorm (scale/shift), residual add, ReLU/LeakyReLU.
 //
-// This header holds the kernel template and its device helpers; conv3d.hip instantiates the tile configurations of
-// the stage -> barrier -> taps form, conv_pipe.hip the persistent LDS-DMA pipelined form (PIPE = 1).
+// This header holds the kernel template and its device helpers; conv_inst_<mode>.hip instantiate the tile configurations,
+// conv3d.hip holds the host side.
 #pragma once
 #include "osa_common.h"
 #include <cstdlib>
@@ -67,7 +67,7 @@ struct ConvArgs {
     int dmin, hmin, wmin;         // min delta per dim
     int LD, LH, LW;               // LDS brick dims (voxels)
     int RowQ, PlaneQ;             // LDS float4s per brick row (padded) / per d-plane (16-byte units keep ds_read_b128)
-    int dbg;                      // debug switch (OSA_DBG): 1 = skip staging (timing experiments only)
+    int dbg;                      // timing ablations (OSA_DBG bits, read through OSA_ABL below): always 0 in the shipped library
     int tilesD, tilesH, tilesW;
     int nchunks, CoP;
     int cps;                      // channel chunks staged per pass (LDS holds cps bricks back to back)
@@ -83,7 +83,6 @@ struct ConvArgs {
     unsigned magicH;              // ceil(2^32/LH)
     int dma;                      // 1: split input + compact LDS image -> stage rows by LDS-DMA (global_load_lds_dwordx4)
     int ringQ;                    // BL kernels: first float4 slot of the B-operand ring inside the workgroup's LDS (above bricks and epilogue tiles)
-    int stag_ticks, stag_n, stag_cus;   // start-up stagger: workgroups with linear id < stag_n wait (id / stag_cus) * stag_ticks 10-ns ticks (0: off)
     // f16x3 range tracking (see osa_f16x3_ranges in the header); every pointer may be NULL.  A "meta" block is
     // OSA_META_FLOATS floats of device memory per tensor: running max |value| in 8 slots (osa_common.h),
     // [1] = power-of-two scale of the stored hi/lo halves when the tensor is a split tensor.
@@ -93,6 +92,23 @@ struct ConvArgs {
     int toff[MAX_TAPS];           // LDS offset of every tap in float4 units (host computed -> scalar loads)
     signed char td[MAX_TAPS], th[MAX_TAPS], tw[MAX_TAPS];
 };
+
+// Timing ablations of conv_mfma_kernel (tools/bench_layers.py --dbgs): the ONE place ConvArgs::dbg is read.  The experiments build
+// (tools/build_variant.sh exp -DOSA_EXPERIMENTS) tests every bit at run time; in the shipped library, where dbg is 0 by construction, the
+// test of every bit outside OSA_ABL_LIVE is the constant 0 and its branch does not reach the ISA.  ConvArgs::dbg itself exists in both
+// builds: the struct layout does not depend on the flag.
+// Bit 8 (no epilogue; tested once per workgroup, outside every loop) stays a run-time test: folded away, the 64-channel redir kernel
+// <f16x3, NCLS 8, REDIR 2>, which sits at 256 VGPRs, spills two more registers (56 -> 64 bytes of scratch per lane; every other
+// instantiation is indifferent to it: profiles/conv_forms_removed/README.md).
+#ifdef OSA_EXPERIMENTS
+constexpr int OSA_ABL_LIVE = ~0;
+#else
+constexpr int OSA_ABL_LIVE = 8;
+#endif
+#define OSA_ABL(p, bits) ((((bits) & OSA_ABL_LIVE) != 0) ? ((p).dbg & (bits)) : 0)
+
+constexpr int OSA_TB = 1;         // wave-private transpose buffers of the epilogue, per wave (kernel and launcher size the LDS by it)
+constexpr int OSA_PD_REDIR = 2;   // tiles whose redir rows are in flight ahead of the tile being finalised (REDIR == 1)
 
 // Stage CC channels [c0, c0+CC) of the input brick into LDS (zero outside the tensor / beyond Ci).
 // Loads are issued U at a time before the first LDS write so a thread keeps U 16-byte loads in flight.
@@ -289,23 +305,13 @@ __device__ __forceinline__ void lds_dma16(const char* src, const unsigned lds_by
                  : "=&s"(keep) : "v"(src), "s"(m0v) : "memory");
 }
 
-// In-kernel timeline (build with -DOSA_EXPERIMENTS -DOSA_TRACE_ON, run with OSA_DBG & 256): wave `w` of every 97th workgroup stamps the 100 MHz wall clock at its
-// phase boundaries into g_trace[slot][wave][event]; tools/trace_conv.py reads it back (osa_debug_trace_read).
-#ifdef OSA_TRACE_ON
-constexpr int TRACE_SLOTS = 32, TRACE_WAVES = 4, TRACE_EVENTS = 40;
-static __device__ unsigned long long g_trace[TRACE_SLOTS * TRACE_WAVES * TRACE_EVENTS];
-#define OSA_TRACE(ev) do { if ((p.dbg & 256) && (tid & 63) == 0 && blockIdx.y == 0 && blockIdx.x % 97 == 0 && blockIdx.x / 97 < TRACE_SLOTS && (tid >> 6) < TRACE_WAVES && (ev) < TRACE_EVENTS) \
-    g_trace[((blockIdx.x / 97) * TRACE_WAVES + (tid >> 6)) * TRACE_EVENTS + (ev)] = wall_clock64(); } while (0)
-#else
-#define OSA_TRACE(ev) do {} while (0)
-#endif
-
 // CFG: MT m-tiles x NT n-tiles per wave, WM x WN waves, brick TD x TH x TW (TD derived)
 // NCLS = 1: ordinary (strided / dilated / 1x1x1) convolution.
 // NCLS = 8: stride-2 transposed convolution, all 8 output-parity classes in one launch: the input
 //           brick is staged once, every class has its own accumulator set and its own run of taps
 //           (class-major tap order, one linear B stream), outputs go to o = 2a + parity.
-template <int PREC, int NCLS, int TU, int MT, int NT, int WM, int WN, int TH, int TW, int REDIR = 0, int OUTS = 0, int PIPE = 0, int KS = 1, int BL = 0>
+template <int PREC, int NCLS, int TU, int MT, int NT, int WM, int WN, int TH, int TW, int REDIR = 0, int OUTS = 0, int /* reserved */ = 0, int KS = 1, int BL = 0>
+// (the unnamed parameter is always 0: it keeps the argument positions, and with them the mangled kernel names that profiles and tools record)
 // BL = 1 (r4): the B (weight) operands of a tap step reach the waves through an LDS ring filled by LDS-DMA -- ONE fetch per workgroup and
 // step instead of one per wave (see the BL block below).  Same products in the same order: bit-identical to BL = 0.
 // OUTS = 1: the output is a split tensor (OSA_OUT_SPLIT) -- separate instantiation: a lane finalises 8
@@ -319,10 +325,6 @@ template <int PREC, int NCLS, int TU, int MT, int NT, int WM, int WN, int TH, in
 // owns the contiguous run of input chunks [g*cpg, (g+1)*cpg) -- its B stream is a contiguous piece of the ordinary packed
 // buffer -- stages its own chunk per pass and accumulates its own partial tiles; the partials meet in LDS and group 0 runs the
 // epilogue.  Host: nchunks % KS == 0, NCLS == 1.
-// PIPE = 1: persistent workgroups walking a list of bricks, the input brick double-buffered in LDS and fed by LDS-DMA
-// (buffer_load ... lds) from a loader wave while the compute waves run the taps of the previous chunk, so staging
-// never waits (see the PIPE block below).  Split (OSA_IN_SPLIT) inputs, compact LDS image, unit input step; 2 workgroups
-// of NW + 1 waves per CU.
 // Waves per SIMD every instantiation is compiled for (its accumulators set the scale: 16 registers per 32x32 tile).  Stated
 // explicitly: left to itself the compiler spends registers on scheduling freedom (the straight-line fast epilogue gives it
 // plenty) and silently drops a wave per SIMD, which costs more than any schedule gains.
@@ -333,28 +335,15 @@ template <int PREC, int NCLS, int TU, int MT, int NT, int WM, int WN, int TH, in
 #ifndef OSA_S2_U
 #define OSA_S2_U 12
 #endif
-#define OSA_S2TILE (NCLS == 1 && WM == 2 && TH == 4 && TW == 8 && !PIPE && KS == 1)
-#define OSA_WAVES_PER_SIMD (PIPE ? 3 : ((NCLS == 8) ? 2 : ((NCLS >= 4) ? 3 : ((OSA_S2TILE && OSA_S2_U > 4) ? 2 : ((MT * NT == 1) ? 4 : ((MT * NT == 2) ? ((MT == 2) ? 4 : 3) : 2))))))
+#define OSA_S2TILE (NCLS == 1 && WM == 2 && TH == 4 && TW == 8 && KS == 1)
+#define OSA_WAVES_PER_SIMD ((NCLS == 8) ? 2 : ((NCLS >= 4) ? 3 : ((OSA_S2TILE && OSA_S2_U > 4) ? 2 : ((MT * NT == 1) ? 4 : ((MT * NT == 2) ? ((MT == 2) ? 4 : 3) : 2)))))
 #define OSA_MIN_BLOCKS OSA_WAVES_PER_SIMD          // HIP: the second __launch_bounds__ argument is waves per SIMD (execution unit)
-__global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM * WN * KS / 4) : OSA_MIN_BLOCKS) void conv_mfma_kernel(const ConvArgs p) {
-    static_assert(KS == 1 || (NCLS == 1 && !PIPE && !REDIR), "split-K: plain convolutions");
-    static_assert(!BL || (KS == 1 && !PIPE && TU == 1), "B ring: one B stream per workgroup, per-tap steps");
+__global__ __launch_bounds__(WM * WN * KS * 64, (KS > 1) ? (WM * WN * KS / 4) : OSA_MIN_BLOCKS) void conv_mfma_kernel(const ConvArgs p) {
+    static_assert(KS == 1 || (NCLS == 1 && !REDIR), "split-K: plain convolutions");
+    static_assert(!BL || (KS == 1 && TU == 1), "B ring: one B stream per workgroup, per-tap steps");
     constexpr int NW = WM * WN;
     constexpr int TD = WM * MT * 32 / (TH * TW);
     static_assert(TD * TH * TW == WM * MT * 32, "brick must hold WM*MT*32 voxels");
-    // XT: "transposed accumulators" -- an r3 experiment, compiled out by default (-DOSA_XT=1 builds it: tools/build_variant.sh).  The plain
-    // f16x3 convolutions that write split tensors issue their MFMAs with the operands swapped (weights as A, activations as B: the same
-    // products summed in the same order -- verified bit-identical on 7 layer shapes, tools/diag_xt.py), so a lane's 16 accumulators of a
-    // 32 x 32 tile are 16 CHANNELS of ONE voxel -- voxel lane & 31, channels (r & 3) + 8 (r >> 2) + 4 hh -- instead of 16 voxels of one
-    // channel.  The epilogue then needs no transpose through LDS (16 ds_write_b32 + 4 ds_read_b128 and two LDS round trips per tile):
-    // one v_permlane32_swap per value pair gives every lane 8 consecutive channels, i.e. the 16-byte hi and lo rows of a split tensor.
-    // MEASURED: the whole model is 14 % SLOWER (155.1 vs 179.9 pairs/s, profiles/round3/ab_xt_epilogue.txt).  A lane then stores 16 B of
-    // a voxel of its own, so a wave's store (and residual load) touches 32 different 128-byte lines instead of 8 whole ones: the
-    // transpose through LDS is what buys coalesced rows, and it is the cheaper of the two.
-#ifndef OSA_XT
-#define OSA_XT 0
-#endif
-    constexpr bool XT = OSA_XT && (PREC == PREC_F16X3) && OUTS && NCLS == 1 && !REDIR && !PIPE && KS == 1;
     static_assert((TW & (TW - 1)) == 0 && (TH & (TH - 1)) == 0, "TH/TW powers of two");
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
 
@@ -365,30 +354,14 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
     const int wm = wave / WN, wn = wave % WN;
     const int col = lane & 31, hh = lane >> 5;
 
-    // current brick: batch item, first a-space position, first input position (fixed per workgroup unless PIPE)
-    int b, a0d, a0h, a0w, g0d, g0h, g0w;
-    auto set_brick = [&](int b_, int tdi, int thi, int twi) {
-        b = b_;
-        a0d = tdi * TD; a0h = thi * TH; a0w = twi * TW;
-        g0d = a0d * p.isd + p.dmin; g0h = a0h * p.ish + p.hmin; g0w = a0w * p.isw + p.wmin;
-    };
-    // PIPE brick order: d fastest, then 4-row strips of h (h % 4, then w, then h / 4), then batch item -- bricks that
-    // run at the same time on one XCD (xcd_remap: 64 consecutive ids) share their halos in d, w and h through its L2
-    auto decode_item = [&](int id, int& b_, int& tdi, int& thi, int& twi) {
-        tdi = id % p.tilesD;
-        const int colid = id / p.tilesD, cpb = p.tilesH * p.tilesW;
-        b_ = colid / cpb;
-        const int c = colid - b_ * cpb, fullrows = p.tilesH & ~3, full = fullrows * p.tilesW;
-        if (c < full) { const int hb = c / (4 * p.tilesW), r = c - hb * 4 * p.tilesW; twi = r >> 2; thi = hb * 4 + (r & 3); }
-        else { const int r = c - full, rem = p.tilesH - fullrows; twi = r / rem; thi = fullrows + r - twi * rem; }
-    };
-    if constexpr (!PIPE) {
-        unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
-        const int twi = bid % p.tilesW; bid /= p.tilesW;
-        const int thi = bid % p.tilesH; bid /= p.tilesH;
-        const int tdi = bid % p.tilesD;
-        set_brick((int)(bid / p.tilesD), tdi, thi, twi);
-    }
+    // this workgroup's brick: batch item, first a-space position, first input position
+    unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int twi = bid % p.tilesW; bid /= p.tilesW;
+    const int thi = bid % p.tilesH; bid /= p.tilesH;
+    const int tdi = bid % p.tilesD;
+    const int b = (int)(bid / p.tilesD);
+    const int a0d = tdi * TD, a0h = thi * TH, a0w = twi * TW;
+    const int g0d = a0d * p.isd + p.dmin, g0h = a0h * p.ish + p.hmin, g0w = a0w * p.isw + p.wmin;
     const int n0 = blockIdx.y * (WN * NT * 32);
 
     // ---- f16x3 operand ranges: power-of-two scales of the input / residual / redir operands and of a split
@@ -423,17 +396,14 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
     }
 
     f32x16 acc[NCLS][MT][NT];
-    auto zero_acc = [&]() {
 #pragma unroll
-        for (int c = 0; c < NCLS; ++c)
+    for (int c = 0; c < NCLS; ++c)
 #pragma unroll
-            for (int m = 0; m < MT; ++m)
+        for (int m = 0; m < MT; ++m)
 #pragma unroll
-                for (int n = 0; n < NT; ++n)
+            for (int n = 0; n < NT; ++n)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[c][m][n][r] = 0.f;
-    };
-    zero_acc();
+                for (int r = 0; r < 16; ++r) acc[c][m][n][r] = 0.f;
 
     // One linear stream of B operands: [chunk][tap][octet] "tap steps" of JO*2*CoP float4 each.
     // Copy-free software pipeline: two static register sets (0/1) ping-pong.  Each half-iteration
@@ -443,7 +413,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
     // "set 0 holds the next group" and no register rotation is ever needed.  The packed buffer
     // carries a few tap steps of slack for the last prefetch.
     const size_t bstep = (size_t)2 * p.CoP;          // float4s per octet
-    const size_t tstep = (p.dbg & 4) ? 0 : (size_t)JO * bstep;   // float4s per tap (dbg 4: stationary B stream, timing only)
+    const size_t tstep = OSA_ABL(p, 4) ? 0 : (size_t)JO * bstep;   // float4s per tap (dbg 4: stationary B stream, timing only)
     const int cpg = (KS > 1) ? p.nchunks / KS : p.nchunks;     // chunks per K group
     const float4* const wp0 = p.w + (size_t)hh * p.CoP + n0 + wn * (NT * 32) + col + (size_t)kg * cpg * p.T * tstep;
     const float4* wp = wp0;
@@ -451,8 +421,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
     constexpr int TUA = RING3 ? 1 : TU;
     static_assert(!RING3 || NCLS == 1, "the B ring needs tap runs that are multiples of 3");
     float4 B0[TUA][JO][NT], B1[TUA][JO][NT], B2[TUA][JO][NT], A0[TUA][JO][MT], A1[TUA][JO][MT];
-    auto init_b = [&]() {                 // B operands of the first tap(s) of the stream (start of a brick)
-        wp = wp0;
+    if constexpr (!BL) {                  // B operands of the first tap(s) of the stream
 #pragma unroll
         for (int u = 0; u < TUA; ++u)
 #pragma unroll
@@ -461,13 +430,8 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
                 for (int n = 0; n < NT; ++n) {
                     B0[u][j][n] = wp[u * tstep + j * bstep + n * 32];
                     if constexpr (RING3) B1[u][j][n] = wp[tstep + j * bstep + n * 32];
-#ifdef OSA_DBG_NOB
-                    B2[u][j][n] = B0[u][j][n];
-                    if constexpr (!RING3) B1[u][j][n] = B0[u][j][n];
-#endif
                 }
-    };
-    if constexpr (!BL) init_b();
+    }
 
     // ---- BL = 1: B operands through an LDS ring (r4).  The r4 ablations (profiles/round4/brick_kernel_without_B_loads_and_amax_retest.txt,
     // march_v1_ablation_and_f16_tests.txt) found the tap loop bound by its weight stream: every wave pulls its own 1 KB fragments through
@@ -529,7 +493,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
 #pragma unroll
             for (int n = 0; n < NT; ++n) Bn[0][j][n] = sl[(j * BL_NBT + wn * NT + n) * 64];
     };
-    if constexpr (BL) { bl_issue(); bl_issue(); bl_issue(); }     // steps 0..2 land while the first brick is staged
+    if constexpr (BL) { bl_issue(); bl_issue(); bl_issue(); }     // steps 0..2 land while the brick is staged
 
     const int brickQ = p.LD * p.PlaneQ;          // float4s per staged chunk
     const int Tm1 = p.T - 1;
@@ -541,14 +505,12 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
 
     // prefetch group starting at flat tap `tn` (B: `skip` tap steps ahead of wp) into (An, Bn)
     auto prefetch = [&](float4 (&An)[TUA][JO][MT], float4 (&Bn)[TUA][JO][NT], int tn, int skip) {
-#ifndef OSA_DBG_NOB          // (-DOSA_DBG_NOB: timing-only build without the per-tap B loads -- what the weight stream through the vector-memory path costs)
 #pragma unroll
         for (int u = 0; u < TUA; ++u)
 #pragma unroll
             for (int j = 0; j < JO; ++j)
 #pragma unroll
                 for (int n = 0; n < NT; ++n) Bn[u][j][n] = wp[(size_t)(skip + u) * tstep + j * bstep + n * 32];
-#endif
 #pragma unroll
         for (int u = 0; u < TUA; ++u) {
             const int ti = tn + u;
@@ -594,15 +556,9 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
                         for (int n = 0; n < NT; ++n) {
                             const f16x8 ah = __builtin_bit_cast(f16x8, Ac[u][0][m]), al = __builtin_bit_cast(f16x8, Ac[u][1][m]);
                             const f16x8 bh = __builtin_bit_cast(f16x8, Bc[u][0][n]), bl = __builtin_bit_cast(f16x8, Bc[u][1][n]);
-                            if constexpr (XT) {          // D^T = W . X^T: lane = voxel, accumulators = channels
-                                ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl, ah, ac[m][n], 0, 0, 0);
-                                ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, al, ac[m][n], 0, 0, 0);
-                                ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh, ah, ac[m][n], 0, 0, 0);
-                            } else {
-                                ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, ac[m][n], 0, 0, 0);
-                                ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, ac[m][n], 0, 0, 0);
-                                ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, ac[m][n], 0, 0, 0);
-                            }
+                            ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, ac[m][n], 0, 0, 0);
+                            ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, ac[m][n], 0, 0, 0);
+                            ac[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, ac[m][n], 0, 0, 0);
                         }
                 }
             }
@@ -619,9 +575,8 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    // taps of ONE staged chunk (sm points at it).  `hook` runs once per tap step between the MFMA groups: the PIPE
-    // form issues one row of the next chunk's LDS-DMA there, so the transfers are spread over the whole tap loop.
-    auto chunk_taps = [&](auto&& hook) {
+    // taps of ONE staged chunk (sm points at it)
+    auto chunk_taps = [&]() {
         // A operands of the first TU taps of this chunk -> set 0 (B0 already holds their B operands)
 #pragma unroll
         for (int u = 0; u < TUA; ++u) {
@@ -636,38 +591,32 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
             // set 0 holds the A operands of the chunk's first tap; its B operands (ring step bl_gs) were published one step ago at the
             // latest (first chunk: by the staging barrier, after the prologue's transfers were waited for)
             bl_read(B0, bl_gs);
-            // BL_B1 (128 x 64 register tiles: 8 accumulator tiles = 128 registers): ONE B register set -- step g + 1's operands are read into
-            // it after step g's MFMAs were issued (the barrier, the transfer and the A reads at the top of the next step cover the LDS
-            // latency); with two sets the tile spills
-            constexpr bool BL_B1 = (MT * NT >= 8);
+            static_assert(MT * NT < 8, "two B register sets: a 128 x 64 register tile would spill");
             auto bl_step = [&](float4 (&An)[TUA][JO][MT], float4 (&Bn)[TUA][JO][NT], const int ta,
                                const float4 (&Ac)[TUA][JO][MT], float4 (&Bc)[TUA][JO][NT], f32x16 (&ac)[MT][NT]) {
                 // (timing-only ablations, experiments build: dbg 1024 no barrier, 2048 no transfers, 4096 no end-of-step wait)
-                if (!(p.dbg & 1024)) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
-                if (!(p.dbg & 2048)) bl_issue();
+                if (!OSA_ABL(p, 1024)) { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
+                if (!OSA_ABL(p, 2048)) bl_issue();
                 const int to = __builtin_amdgcn_readlane(toff_v, (ta < Tm1) ? ta : Tm1);
 #pragma unroll
                 for (int j = 0; j < JO; ++j)
 #pragma unroll
                     for (int m = 0; m < MT; ++m) An[0][j][m] = sm[abase[m] + to + j * 2];
-                if constexpr (!BL_B1) bl_read(Bn, bl_gs + 1);
+                bl_read(Bn, bl_gs + 1);
                 __builtin_amdgcn_sched_barrier(0);
                 compute(Ac, Bc, ac, 1);
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (BL_B1) bl_read(Bc, bl_gs + 1);
-                if (!(p.dbg & 4096)) wait_vmcnt(BL_NIW);
+                if (!OSA_ABL(p, 4096)) wait_vmcnt(BL_NIW);
                 ++bl_gs;
             };
 #pragma unroll
             for (int c = 0; c < NCLS; ++c) {
                 const int tend = (NCLS == 1) ? p.T : p.cls_end[c];
                 while (t < tend) {
-                    hook();
-                    if constexpr (BL_B1) bl_step(A1, B0, t + 1, A0, B0, acc[c]); else bl_step(A1, B1, t + 1, A0, B0, acc[c]);
+                    bl_step(A1, B1, t + 1, A0, B0, acc[c]);
                     ++t;
                     if (t < tend) {
-                        hook();
-                        if constexpr (BL_B1) bl_step(A0, B0, t + 1, A1, B0, acc[c]); else bl_step(A0, B0, t + 1, A1, B1, acc[c]);
+                        bl_step(A0, B0, t + 1, A1, B1, acc[c]);
                         ++t;
                     }
                     else {
@@ -686,13 +635,13 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
             // Three steps are one full turn of the B ring, so leaving after the first triple keeps
             // the invariant for the next chunk (whose A0 is reloaded anyway).
             for (; t < p.T; t += 6) {
-                hook(); ring_step(A1, t + 1, B2, 2, A0, B0);
-                hook(); ring_step(A0, t + 2, B0, 3, A1, B1);
-                hook(); ring_step(A1, t + 3, B1, 4, A0, B2);
+                ring_step(A1, t + 1, B2, 2, A0, B0);
+                ring_step(A0, t + 2, B0, 3, A1, B1);
+                ring_step(A1, t + 3, B1, 4, A0, B2);
                 if (t + 3 >= p.T) { wp += (size_t)3 * tstep; break; }
-                hook(); ring_step(A0, t + 4, B2, 5, A1, B0);
-                hook(); ring_step(A1, t + 5, B0, 6, A0, B1);
-                hook(); ring_step(A0, t + 6, B1, 7, A1, B2);
+                ring_step(A0, t + 4, B2, 5, A1, B0);
+                ring_step(A1, t + 5, B0, 6, A0, B1);
+                ring_step(A0, t + 6, B1, 7, A1, B2);
                 wp += (size_t)6 * tstep;
             }
         } else {
@@ -701,14 +650,12 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
                 const int tend = (NCLS == 1) ? p.T : p.cls_end[c];
                 while (t < tend) {
                     const int cnt0 = (tend - t < TU) ? (tend - t) : TU;
-                    hook();
                     prefetch(A1, B1, t + cnt0, cnt0);
                     __builtin_amdgcn_sched_barrier(0);
                     compute(A0, B0, acc[c], cnt0);
                     __builtin_amdgcn_sched_barrier(0);
                     wp += (size_t)cnt0 * tstep; t += cnt0;
                     const int cnt1 = (tend - t < TU) ? (tend - t) : TU;     // 0 when the run had an odd number of groups
-                    hook();
                     prefetch(A0, B0, t + cnt1, cnt1);
                     __builtin_amdgcn_sched_barrier(0);
                     compute(A1, B1, acc[c], cnt1);
@@ -719,36 +666,18 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
         }
     };
 
-    // ---- start-up stagger (de-phasing).  Every workgroup of a launch does the same work in the same time, so the workgroups that
-    // share a CU -- and with them the whole chip -- march through "stage (HBM) -> taps (MFMA) -> epilogue (HBM)" in lock step: the
-    // matrix pipes idle while everybody stages or stores, HBM idles while everybody runs taps, and the launch costs the SUM of
-    // its phases although 2-4 workgroups per CU could overlap them (in-kernel timeline, profiles/round2/deconv_epilogue.txt).  The
-    // workgroups of the first dispatch wave that land in residency slot s of their CU (dispatch order: slot = linear id / #CUs)
-    // start s * stag_ticks later (100 MHz wall clock); their successors inherit the phase because every workgroup lasts equally long.
-    if (p.stag_ticks) {
-        const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-        if (lin < (unsigned)p.stag_n) {
-            const unsigned slot = lin / (unsigned)p.stag_cus;
-            if (slot) {
-                const unsigned long long t0 = wall_clock64(), ticks = (unsigned long long)slot * (unsigned)p.stag_ticks;
-                while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-            }
-        }
-    }
-    OSA_TRACE(0);
-    [[maybe_unused]] int trace_ev = 1;
     if constexpr (KS > 1) {
         // split-K: pass i stages chunk kg*cpg + i of every group (each group with its own NW*64 threads, into its own LDS slot)
         const int tid_g = tid - kg * (NW * 64);
         for (int i = 0; i < cpg; ++i) {
             if (i) __syncthreads();
-            if (!(p.dbg & 1)) {
+            if (!OSA_ABL(p, 1)) {
                 if (PREC == PREC_F16 && !(p.act & OSA_IN_SPLIT)) stage_brick_cvt16<NW * 64, 1>(p, smem + kg * brickQ, brickQ, b, (kg * cpg + i) * CC, g0d, g0h, g0w, tid_g);
                 else stage_brick<NW * 64, PREC, 1>(p, smem + kg * brickQ, brickQ, b, (kg * cpg + i) * CC, g0d, g0h, g0w, tid_g, s_in);
             }
             __syncthreads();
             sm = smem + kg * brickQ;
-            chunk_taps([]() {});
+            chunk_taps();
         }
         // partial tiles of groups 1 .. KS-1 -> LDS (lane-contiguous: [group][wave][tile][register][lane]); group 0 adds them up
         __syncthreads();                                   // every group is done with the bricks
@@ -774,22 +703,21 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
                         for (int r = 0; r < 16; ++r)
                             acc[0][m][n][r] += red[((((g * NW + wave) * NIK + m * NT + n) * 16) + r) * 64 + lane];
         }
-    } else if constexpr (!PIPE) {
+    } else {
     for (int ch0 = 0; ch0 < p.nchunks; ch0 += p.cps) {
         if (ch0) __syncthreads();
-        OSA_TRACE(trace_ev); ++trace_ev;                 // pass start (after the previous pass's readers are done)
         const int ncl = (p.nchunks - ch0 < p.cps) ? (p.nchunks - ch0) : p.cps;
-        if (!(p.dbg & 1) && PREC != PREC_F32 && p.dma) {
+        if (!OSA_ABL(p, 1) && PREC != PREC_F32 && p.dma) {
             for (int cl = 0; cl < ncl; ++cl)
                 stage_brick_dma<NW * 64>(p, smem + cl * brickQ, b, (ch0 + cl) * CC, g0d, g0h, g0w, tid);
-        } else if (!(p.dbg & 1) && PREC == PREC_F16 && !(p.act & OSA_IN_SPLIT)) {
+        } else if (!OSA_ABL(p, 1) && PREC == PREC_F16 && !(p.act & OSA_IN_SPLIT)) {
             constexpr int SU = OSA_S2TILE ? OSA_S2_U : OSA_STAGE_U;
             int cl = 0;
             for (; cl + 2 <= ncl; cl += 2)
                 stage_brick_cvt16<NW * 64, 2, SU>(p, smem + cl * brickQ, brickQ, b, (ch0 + cl) * CC, g0d, g0h, g0w, tid);
             if (cl < ncl)
                 stage_brick_cvt16<NW * 64, 1, SU>(p, smem + cl * brickQ, brickQ, b, (ch0 + cl) * CC, g0d, g0h, g0w, tid);
-        } else if (!(p.dbg & 1)) {
+        } else if (!OSA_ABL(p, 1)) {
             constexpr int SU = OSA_S2TILE ? OSA_S2_U : OSA_STAGE_U;
             int cl = 0;
             for (; cl + 2 <= ncl; cl += 2)
@@ -797,15 +725,12 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
             if (cl < ncl)
                 stage_brick<NW * 64, PREC, 1, SU>(p, smem + cl * brickQ, brickQ, b, (ch0 + cl) * CC, g0d, g0h, g0w, tid, s_in);
         }
-        OSA_TRACE(trace_ev); ++trace_ev;                 // own staging loads issued + written
         if constexpr (BL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // ring transfers issued through inline asm: invisible to the compiler's own counts
         __syncthreads();
-        OSA_TRACE(trace_ev); ++trace_ev;                 // brick complete
         for (int cl = 0; cl < ncl; ++cl) {
             sm = smem + cl * brickQ;
-            chunk_taps([]() {});
+            chunk_taps();
         }
-        OSA_TRACE(trace_ev); ++trace_ev;                 // taps done
     }
     }
 
@@ -837,10 +762,9 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
     }
     if (p.out_meta) amax_seen = amax_peek(p.out_meta);   // early: its latency hides behind the epilogue
     if constexpr (BL) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's run-ahead transfers: the fast path below counts its own loads only
-    if constexpr (!PIPE) __syncthreads();              // everyone is done reading the input brick (PIPE: the chunk's end barrier)
-    OSA_TRACE(20);
+    __syncthreads();                                   // everyone is done reading the input brick
     if (KS > 1 && kg != 0) return;                     // split-K: group 0 holds the sums (the others rejoin at publish_amax)
-    if (p.dbg & 8) {                                   // timing only: no epilogue (keeps the accumulators live)
+    if (OSA_ABL(p, 8)) {                                 // timing only: no epilogue (keeps the accumulators live)
         float s = 0.f;
 #pragma unroll
         for (int c = 0; c < NCLS; ++c)
@@ -853,9 +777,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
         if (s == 12345.678f) p.y[0] = s;
         return;
     }
-#ifndef OSA_TB
-#define OSA_TB 1                                   // transpose buffers per wave (2: tile i+1's transpose may start while tile i is finalised)
-#endif
     float* const tb0 = tbase + wave * (OSA_TB * 32 * 36);
     // per-batch-item base pointers (wave-uniform, 64-bit); everything per lane is a 32-bit element offset
     const size_t bvox = (size_t)b * p.Do * p.Ho * p.Wo;
@@ -890,16 +811,13 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
     // code everywhere: its 4-waves-per-SIMD tiles would spill.
     constexpr bool FASTC = (PREC != PREC_F32) && (REDIR != 2) && !(NCLS == 1 && MT == 2 && NT == 1);
     const bool fast = FASTC && (a0d + TD <= p.Ad) && (a0h + TH <= p.Ah) && (a0w + TW <= p.Aw) && (n0 + WN * NT * 32 <= p.Co) &&
-                      vec4 && !p.gate && actk <= OSA_ACT_RELU6 && !(p.act & OSA_RES_AFTER_ACT) && !(p.dbg & (32 | 64));
+                      vec4 && !p.gate && actk <= OSA_ACT_RELU6 && !(p.act & OSA_RES_AFTER_ACT) && !OSA_ABL(p, 32 | 64);
     // A wave finalises NI = MT*NCLS*NT tiles of 32 voxels x 32 channels one after the other.  The
     // residual rows of tile i+PD are requested before tile i is processed (rolling window of PD
     // tiles, static register sets), so the HBM round trip of a residual overlaps the LDS transposes,
     // arithmetic and stores of the PD-1 tiles in front of it -- the fused transposed conv has 8 tiles
     // per wave and spent half of its time waiting for them one by one.
     constexpr int NI = MT * NCLS * NT;
-#ifndef OSA_PD_REDIR
-#define OSA_PD_REDIR 2
-#endif
     constexpr int PD = REDIR ? ((REDIR == 1) ? OSA_PD_REDIR : 2) : ((NCLS >= 4) ? ((PREC != PREC_F32 && NCLS == 8) ? 2 : 3) : ((NI < 2) ? NI : 2));
     // voxel bookkeeping of the 4 rows (vsub + 8k) this lane finalises in M tile m
     auto rows_of = [&](auto F, int m, int (&v0)[4], int (&g0)[4], bool (&vok)[4]) {
@@ -909,7 +827,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
             const int q = (wm * MT + m) * 32 + vsub + 8 * k;
             const int ad = a0d + q / (TW * TH), ah = a0h + (q / TW) % TH, aw = a0w + q % TW;
             vok[k] = FULL || (ad < p.Ad && ah < p.Ah && aw < p.Aw);
-            const int os_ = (!FULL && (p.dbg & 64)) ? 1 : p.os;                // dbg 64: contiguous rows (timing only)
+            const int os_ = (!FULL && OSA_ABL(p, 64)) ? 1 : p.os;                // dbg 64: contiguous rows (timing only)
             v0[k] = ((ad * os_) * p.Ho + ah * os_) * p.Wo + aw * os_;          // voxel index inside batch item b (host: < 2^31 elements)
             g0[k] = (ah * p.os) * p.Wo + aw * p.os;
         }
@@ -918,7 +836,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
         const int ood = (NCLS == 1) ? p.ood : ((c >> 2) & 1), ooh = (NCLS == 1) ? p.ooh : ((c >> 1) & 1),
                   oow = (NCLS == 1) ? p.oow : (c & 1);
         coff = (ood * p.Ho + ooh) * p.Wo + oow;              // supported transposed convs: Do == 2*Di
-        if (p.dbg & 64) coff = ood * (p.Ad * p.Ho * p.Wo) + (ooh * 2 + oow) * TW;
+        if (OSA_ABL(p, 64)) coff = ood * (p.Ad * p.Ho * p.Wo) + (ooh * 2 + oow) * TW;
         goff = ooh * p.Wo + oow;
     };
     // tile order: m outer, class, n inner
@@ -1021,7 +939,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
                 store16(yb + (v0[k] + coff) * p.yCs + co, make_float4(o[0], o[1], o[2], o[3]));
                 continue;
             }
-            if (vok[k] && cok && !(p.dbg & 32)) {             // dbg 32: no stores (timing only)
+            if (vok[k] && cok && !OSA_ABL(p, 32)) {             // dbg 32: no stores (timing only)
                 float* yp = yb + (v0[k] + coff) * p.yCs + co;
                 if (vec4) {
                     am = fmaxf(am, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
@@ -1046,7 +964,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
             const int q = (wm * MT + m) * 32 + vs2 + 16 * k;
             const int ad = a0d + q / (TW * TH), ah = a0h + (q / TW) % TH, aw = a0w + q % TW;
             vok[k] = FULL || (ad < p.Ad && ah < p.Ah && aw < p.Aw);
-            const int os_ = (!FULL && (p.dbg & 64)) ? 1 : p.os;
+            const int os_ = (!FULL && OSA_ABL(p, 64)) ? 1 : p.os;
             v0[k] = ((ad * os_) * p.Ho + ah * os_) * p.Wo + aw * os_;
         }
     };
@@ -1131,7 +1049,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
                     hq[h2] = __builtin_bit_cast(uint2, q); lq[h2] = hq[h2];
                 } else split_f16(make_float4(o[0] * s_out, o[1] * s_out, o[2] * s_out, o[3] * s_out), hq[h2], lq[h2]);
             }
-            if (FULL || (vok[k] && cok && !(p.dbg & 32))) {
+            if (FULL || (vok[k] && cok && !OSA_ABL(p, 32))) {
                 if constexpr (PREC == PREC_F16) {
                     store16(yb + (v0[k] + coff) * p.yCs + (co >> 1), make_uint4(hq[0].x, hq[0].y, hq[1].x, hq[1].y));     // yCs in float units
                 } else {
@@ -1278,7 +1196,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
                         bn8(i % NT, sc8, sh8);
                         finish8(F, i, zero4, sc8, sh8);
                     } else finish(F, i, zero4);
-                    OSA_TRACE(21 + i);
                     __builtin_amdgcn_sched_barrier(0);       // tiles are scheduled one at a time (the prefetch depth PD is explicit): bounds live ranges
                 }
             };
@@ -1286,124 +1203,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
             else run(std::false_type{});
         }
     }
-    if constexpr (XT) {
-        // ---- transposed-accumulator epilogue: lane (col, hh) owns voxel `col` of M tile m; per 16-channel block P of the N tile it holds
-        // channels 16P + 4hh + {0..3} (accumulators 8P .. 8P+3) and 16P + 8 + 4hh + {0..3} (8P+4 .. 8P+7).  v_permlane32_swap exchanges the
-        // first quad of the hh = 1 lanes with the second quad of the hh = 0 lanes: afterwards a lane holds the 8 CONSECUTIVE channels
-        // 16P + 8hh .. + 7 -- one 16-byte row of hi halves and one of lo halves in the split layout, like the residual it reads.
-        auto rowT = [&](auto F, int m, int& v0, bool& vok) {
-            constexpr bool FULL = decltype(F)::value;
-            const int q = (wm * MT + m) * 32 + col;
-            const int ad = a0d + q / (TW * TH), ah = a0h + (q / TW) % TH, aw = a0w + q % TW;
-            vok = FULL || (ad < p.Ad && ah < p.Ah && aw < p.Aw);
-            const int os_ = (!FULL && (p.dbg & 64)) ? 1 : p.os;
-            v0 = ((ad * os_) * p.Ho + ah * os_) * p.Wo + aw * os_;
-        };
-        auto load_res8T = [&](auto F, int i, float4 (&rv)[4]) {
-            constexpr bool FULL = decltype(F)::value;
-            const int n = i % NT, m = i / NT;
-            int v0, coff, goff; bool vok;
-            rowT(F, m, v0, vok);
-            class_off(0, coff, goff);
-#pragma unroll
-            for (int P = 0; P < 2; ++P) {
-                const int co = n0 + (wn * NT + n) * 32 + 16 * P + 8 * hh;
-                const int off = (v0 + coff) * p.rCs + (co >> 4) * 16 + ((co & 15) >> 3) * 4;
-                if constexpr (FULL) {
-                    const float* rs = rbase + (off & rmask);
-                    rv[2 * P] = *reinterpret_cast<const float4*>(rs);
-                    rv[2 * P + 1] = *reinterpret_cast<const float4*>(rs + 8);
-                    continue;
-                }
-                rv[2 * P] = make_float4(0.f, 0.f, 0.f, 0.f); rv[2 * P + 1] = rv[2 * P];
-                if (p.res && vok && co < p.Co) {
-                    rv[2 * P] = *reinterpret_cast<const float4*>(resb + off);            // 8 hi halves
-                    rv[2 * P + 1] = *reinterpret_cast<const float4*>(resb + off + 8);    // 8 lo halves
-                }
-            }
-        };
-        auto finish8T = [&](auto F, int i, const float4 (&rv)[4], const float4 (&sc8)[2][2], const float4 (&sh8)[2][2]) {
-            constexpr bool FULL = decltype(F)::value;
-            const int n = i % NT, m = i / NT;
-            int v0, coff, goff; bool vok;
-            rowT(F, m, v0, vok);
-            class_off(0, coff, goff);
-#pragma unroll
-            for (int P = 0; P < 2; ++P) {
-                const int co = n0 + (wn * NT + n) * 32 + 16 * P + 8 * hh;
-                const bool cok = FULL || co < p.Co;
-                float a8[2][4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {         // executed by all 64 lanes (no lane-dependent branch around it)
-                    // (__float_as_uint of a scalar copy: __builtin_bit_cast applied to the vector element itself makes this clang fold every
-                    // swap of the tile onto accumulator 0 -- tools/experiments note in profiles/DESIGN_rounds1-5.md 3.2 r3)
-                    const float xf = acc[0][m][n][8 * P + e], yf = acc[0][m][n][8 * P + 4 + e];
-                    const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(xf), __float_as_uint(yf), false, false);
-                    a8[0][e] = __uint_as_float(sw[0]); a8[1][e] = __uint_as_float(sw[1]);
-                }
-                uint2 hq[2], lq[2];
-#pragma unroll
-                for (int h2 = 0; h2 < 2; ++h2) {
-                    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (FULL || p.res) {
-                        const uint4 hb = __builtin_bit_cast(uint4, rv[2 * P]), lb = __builtin_bit_cast(uint4, rv[2 * P + 1]);
-                        r = h2 ? join_f16(make_uint2(hb.z, hb.w), make_uint2(lb.z, lb.w)) : join_f16(make_uint2(hb.x, hb.y), make_uint2(lb.x, lb.y));
-                        r = mul4(r, s_res_inv);
-                        if constexpr (FULL) r = make_float4(has_res ? r.x : 0.f, has_res ? r.y : 0.f, has_res ? r.z : 0.f, has_res ? r.w : 0.f);
-                    }
-                    const float s4[4] = {sc8[P][h2].x, sc8[P][h2].y, sc8[P][h2].z, sc8[P][h2].w}, t4[4] = {sh8[P][h2].x, sh8[P][h2].y, sh8[P][h2].z, sh8[P][h2].w};
-                    const float r4[4] = {r.x, r.y, r.z, r.w};
-                    float o[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = fmaf(a8[h2][e], s4[e], t4[e]) + r4[e];
-                        if constexpr (FULL) { o[e] = act_cheap(v); continue; }
-                        if (actk == OSA_ACT_RELU) v = fmaxf(v, 0.f);
-                        else if (actk == OSA_ACT_LEAKY) v = (v > 0.f) ? v : v * p.slope;
-                        else if (actk == OSA_ACT_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-                        else if (actk == OSA_ACT_SIGMOID) v = 1.0f / (1.0f + expf(-v));
-                        else if (actk == OSA_ACT_TANH) v = tanhf(v);
-                        o[e] = v;
-                    }
-                    if (vok && cok) am = fmaxf(am, fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))));
-                    split_f16(make_float4(o[0] * s_out, o[1] * s_out, o[2] * s_out, o[3] * s_out), hq[h2], lq[h2]);
-                }
-                if (FULL || (vok && cok && !(p.dbg & 32))) {
-                    float* ys = yb + (v0 + coff) * p.yCs + (co >> 4) * 16 + ((co & 15) >> 3) * 4;
-                    store16(ys, make_uint4(hq[0].x, hq[0].y, hq[1].x, hq[1].y));
-                    store16(ys + 8, make_uint4(lq[0].x, lq[0].y, lq[1].x, lq[1].y));
-                }
-            }
-        };
-        float4 sc8[NT][2][2], sh8[NT][2][2];
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int P = 0; P < 2; ++P)
-#pragma unroll
-                for (int h2 = 0; h2 < 2; ++h2) {
-                    const int co = n0 + (wn * NT + n) * 32 + 16 * P + 8 * hh + 4 * h2;
-                    sc8[n][P][h2] = make_float4(osc, osc, osc, osc); sh8[n][P][h2] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (co + 3 < p.Co && p.scale) {
-                        sc8[n][P][h2] = *reinterpret_cast<const float4*>(p.scale + co); sh8[n][P][h2] = *reinterpret_cast<const float4*>(p.shift + co);
-                        sc8[n][P][h2].x *= osc; sc8[n][P][h2].y *= osc; sc8[n][P][h2].z *= osc; sc8[n][P][h2].w *= osc;
-                    }
-                }
-        auto run = [&](auto F) {
-#pragma unroll
-            for (int i = 0; i < PD; ++i) load_res8T(F, i, rvb[i]);
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                finish8T(F, i, rvb[i % PD], sc8[i % NT], sh8[i % NT]);
-                if (i + PD < NI) load_res8T(F, i + PD, rvb[i % PD]);
-                OSA_TRACE(21 + i);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        if constexpr (FASTC) { if (fast) run(std::true_type{}); else run(std::false_type{}); }
-        else run(std::false_type{});
-    }
-    if constexpr (!REDIR && OUTS && !XT) {
+    if constexpr (!REDIR && OUTS) {
         float4 sc8[NT][2], sh8[NT][2];
 #pragma unroll
         for (int n = 0; n < NT; ++n) bn8(n, sc8[n], sh8[n]);
@@ -1414,7 +1214,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
             for (int i = 0; i < NI; ++i) {
                 finish8(F, i, rvb[i % PD], sc8[i % NT], sh8[i % NT]);
                 if (i + PD < NI) load_res8(F, i + PD, rvb[i % PD]);
-                OSA_TRACE(21 + i);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -1429,7 +1228,6 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
             for (int i = 0; i < NI; ++i) {
                 finish(F, i, rvb[i % PD]);
                 if (i + PD < NI) load_res(F, i + PD, rvb[i % PD]);
-                OSA_TRACE(21 + i);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
@@ -1438,120 +1236,7 @@ __global__ __launch_bounds__(WM * WN * KS * 64 + (PIPE ? 64 : 0), (KS > 1) ? (WM
     }
     };   // epilogue
 
-    if constexpr (!PIPE) {
-        epilogue(reinterpret_cast<float*>(smem));
-    } else {
-        static_assert(NCLS == 1 && !REDIR && PREC == PREC_F16X3, "PIPE: plain f16x3 convolutions");
-        // ---- persistent, LDS-DMA pipelined form ------------------------------------------------------------------
-        // The workgroup (NW compute waves + ONE loader wave) walks bricks id = xcd_remap(blockIdx.x) + k * gridDim.x.  Two
-        // LDS buffers hold chunk gc and chunk gc + 1 of the running (brick, 16-channel chunk) sequence.  While the compute
-        // waves run the taps of chunk gc, the loader wave streams chunk gc + 1 into the other buffer: one
-        // `buffer_load_dwordx4 ... lds` per (d, h) row of the brick, straight from the split tensor in HBM/L2 -- no VGPR
-        // round trip, no ds_write; a per-row buffer descriptor with num_records = row bytes (0 for rows outside the
-        // tensor) makes the hardware zero-fill every out-of-range voxel.  The loader is a wave of its own because vmcnt
-        // retires in order: with the DMA in the compute waves' queue every wait for a B operand (an L2 hit) would also
-        // wait for the DMA rows in front of it (measured: -14 %).  One barrier per chunk publishes the landed buffer (the
-        // loader waits vmcnt(0) first); the epilogue transposes through the buffer that was just consumed and one more
-        // barrier keeps the next DMA out of it.  Staging is off the critical path; the epilogue of one workgroup overlaps
-        // the taps of the other workgroup on the CU.
-        const int G = (int)gridDim.x;
-        const int nitems = p.B * p.tilesD * p.tilesH * p.tilesW;
-        int item = (int)xcd_remap(blockIdx.x, (unsigned)G);
-        int gc = 0;
-        if (wave == NW) {
-            // ================= loader wave =================
-            const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;
-            const unsigned bufbytes = (unsigned)brickQ * 16u;
-            const unsigned rowbytes = (unsigned)(p.Wi * p.xCs) * 4u;
-            const long long planebytes = (long long)p.Hi * rowbytes;
-            const size_t itembytes = (size_t)p.Di * planebytes;
-            const int lw_ = lane >> 2, c4_ = lane & 3;
-            const bool lane_in = lw_ < p.LW;
-            auto dma_chunk = [&](int b_, int c0, int gd0, int gh0, int gw0, unsigned ldsbuf) {
-                if (p.dbg & 1) return;                                   // experiments: no staging (timing only)
-                const char* base = reinterpret_cast<const char*>(p.x) + (size_t)b_ * itembytes + (size_t)c0 * 4;
-                const unsigned voff = (unsigned)((gw0 + lw_) * p.xCs * 4 + c4_ * 16);    // left of / beyond the row: >= num_records -> 0
-                for (int ld = 0; ld < p.LD; ++ld) {
-                    const int gd = gd0 + ld;
-                    const bool dok = (unsigned)gd < (unsigned)p.Di;
-                    const char* rowp = base + (long long)gd * planebytes + (long long)gh0 * rowbytes;
-                    unsigned ldsrow = ldsbuf + (unsigned)(ld * p.PlaneQ) * 16u;
-                    for (int lh = 0; lh < p.LH; ++lh, rowp += rowbytes, ldsrow += (unsigned)p.RowQ * 16u) {
-                        const bool ok = dok && ((unsigned)(gh0 + lh) < (unsigned)p.Hi);
-                        const unsigned long long rp = (unsigned long long)rowp;
-                        u32x4 srd;
-                        srd.x = __builtin_amdgcn_readfirstlane((unsigned)rp);
-                        srd.y = __builtin_amdgcn_readfirstlane((unsigned)(rp >> 32));
-                        srd.z = __builtin_amdgcn_readfirstlane(ok ? rowbytes : 0u);
-                        srd.w = 0x00020000u;
-                        const unsigned m0v = __builtin_amdgcn_readfirstlane(ldsrow);
-                        if (lane_in) {
-                            unsigned keep;
-                            asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                                         "buffer_load_dwordx4 %2, %1, 0 offen lds\n\ts_mov_b32 m0, %0"
-                                         : "=&s"(keep) : "s"(srd), "v"(voff), "s"(m0v) : "memory");
-                        }
-                    }
-                }
-            };
-            auto land = [&]() {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every row of the chunk has landed in LDS ...
-                __syncthreads();                                        // ... hand it to the compute waves (their chunk-end barrier)
-            };
-            if (item < nitems) {
-                int b_, td_, th_, tw_;
-                decode_item(item, b_, td_, th_, tw_);
-                set_brick(b_, td_, th_, tw_);
-                dma_chunk(b, 0, g0d, g0h, g0w, lds0);
-            }
-            land();
-            while (item < nitems) {
-                const int nitem = item + G;
-                for (int ch = 0; ch < p.nchunks; ++ch, ++gc) {
-                    const unsigned nbuf = lds0 + (unsigned)((gc + 1) & 1) * bufbytes;
-                    if (ch + 1 < p.nchunks) dma_chunk(b, (ch + 1) * CC, g0d, g0h, g0w, nbuf);
-                    else if (nitem < nitems) {
-                        int b_, td_, th_, tw_;
-                        decode_item(nitem, b_, td_, th_, tw_);
-                        dma_chunk(b_, 0, td_ * TD * p.isd + p.dmin, th_ * TH * p.ish + p.hmin, tw_ * TW * p.isw + p.wmin, nbuf);
-                    }
-                    land();
-                }
-                __syncthreads();                                        // (the compute waves' post-epilogue barrier)
-                item = nitem;
-                if (item < nitems) {
-                    int b_, td_, th_, tw_;
-                    decode_item(item, b_, td_, th_, tw_);
-                    set_brick(b_, td_, th_, tw_);
-                }
-            }
-        } else {
-            // ================= compute waves =================
-            if (item < nitems) {
-                int b_, td_, th_, tw_;
-                decode_item(item, b_, td_, th_, tw_);
-                set_brick(b_, td_, th_, tw_);
-            }
-            __syncthreads();                                            // chunk 0 of the first brick has landed
-            while (item < nitems) {
-                zero_acc();
-                init_b();
-                for (int ch = 0; ch < p.nchunks; ++ch, ++gc) {
-                    sm = smem + (size_t)(gc & 1) * brickQ;
-                    if (!(p.dbg & 16)) chunk_taps([]() {});             // (experiments: dbg 16 = no taps, timing only)
-                    __syncthreads();                                    // chunk gc is consumed, chunk gc + 1 has landed
-                }
-                epilogue(reinterpret_cast<float*>(smem + (size_t)((gc - 1) & 1) * brickQ));
-                __syncthreads();                                        // the epilogue's transpose tiles are free again
-                item += G;
-                if (item < nitems) {
-                    int b_, td_, th_, tw_;
-                    decode_item(item, b_, td_, th_, tw_);
-                    set_brick(b_, td_, th_, tw_);
-                }
-            }
-        }
-    }
+    epilogue(reinterpret_cast<float*>(smem));
     // ---- publish max |output| of this wave into the output's range block
     if (p.out_meta) publish_amax(p.out_meta, am, amax_seen, reinterpret_cast<float*>(smem));   // (barrier inside: every wave is past its tiles)
 }

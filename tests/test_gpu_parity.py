@@ -835,7 +835,7 @@ def test_igev_refine_loop_vs_reference_golden(prec):
     close(out["net_list"][0], g["net0"], atol=1e-4, rtol=1e-4, what=f"hidden state [{prec}]")
 
 
-# ----------------------------------------------------------------------------- persistent LDS-DMA pipelined conv (PIPE)
+# ----------------------------------------------------------------------------- convs on split inputs (bricks staged by LDS-DMA)
 PIPE_CASES = [
     # name, Ci, Co, k, pad, dil, (B, D, H, W), residual (None | "split" | "plain"), split output
     ("32-32 k3 ragged", 32, 32, 3, 1, 1, (2, 7, 13, 19), None, True),
@@ -851,9 +851,9 @@ PIPE_CASES = [
 
 @pytest.mark.parametrize("case", PIPE_CASES, ids=[c[0] for c in PIPE_CASES])
 def test_pipelined_conv_on_split_inputs_vs_torch(case):
-    """Stride-1 f16x3 convs whose input is a split tensor run as persistent workgroups with the brick double-buffered in
-    LDS by LDS-DMA (conv_kernel.h, PIPE): ragged volumes (zero fill by the buffer descriptor), several bricks per workgroup,
-    several batch items, split / plain residuals and outputs -- against torch, and bit-identical when repeated."""
+    """Stride-1 f16x3 convs whose input is a split tensor (their bricks are staged by LDS-DMA, conv_kernel.h stage_brick_dma; the cases were
+    written for the persistent pipelined form, which was measured slower and is gone: DESIGN.md 3.2): ragged volumes (zero fill outside the
+    tensor), several bricks, several batch items, split / plain residuals and outputs -- against torch, and bit-identical when repeated."""
     from openstereo_amd import ops
     from openstereo_amd.engine import PackedConv3d, is_split
     name, Ci, Co, k, pad, dil, (B, D, H, W), res_kind, out_split = case

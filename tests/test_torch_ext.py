@@ -82,6 +82,28 @@ def test_volume_and_head_gradients_are_defined_once():
     assert sum(t.count("\n") for t in texts.values()) < 6881
 
 
+def test_conv_sources_hold_no_rejected_kernel_form():
+    """The brick convolution's sources carry the forms that ship and nothing else ("Removed forms"): no persistent PIPE form, no
+    transposed-accumulator epilogue, no start-up stagger, no in-kernel timeline, no build without B loads, no single-B-set ring step, and
+    the timing ablations read ConvArgs::dbg through the one macro that is the constant 0 in the shipped build."""
+    import re
+    names = ("conv_kernel.h", "conv3d.hip", "conv_inst_impl.h", "conv_cfgs.def")
+    texts = {n: open(os.path.join(ROOT, "openstereo_amd", "csrc", n)).read() for n in names}
+    gone = re.compile(r"(?<![A-Za-z0-9_])PIPE(?![A-Za-z0-9_])|OSA_XT|stag_|OSA_TRACE|OSA_DBG_NOB|BL_B1|launch_conv_pipe")
+    offenders = [f"{n}:{i + 1}: {m.group(0)}" for n, t in texts.items() for i, line in enumerate(t.split("\n")) for m in gone.finditer(line)]
+    assert not offenders, offenders
+    # ConvArgs::dbg is read in one place, the definition of OSA_ABL; outside the experiments build only the bits of OSA_ABL_LIVE are tested
+    # at run time (bit 8, once per workgroup: conv_kernel.h says why), every other test is the constant 0
+    reads = [f"{n}:{i + 1}: {line.strip()}" for n, t in texts.items() for i, line in enumerate(t.split("\n"))
+             if re.search(r"p\)?\.dbg", line)]
+    assert len(reads) == 1 and reads[0].startswith("conv_kernel.h") and "#define OSA_ABL(p, bits)" in reads[0], reads
+    assert "((bits) & OSA_ABL_LIVE) != 0) ? ((p).dbg & (bits)) : 0" in reads[0], reads
+    live = re.search(r"#ifdef OSA_EXPERIMENTS\nconstexpr int OSA_ABL_LIVE = ~0;\n#else\nconstexpr int OSA_ABL_LIVE = (\d+);\n#endif\n", texts["conv_kernel.h"])
+    assert live and int(live.group(1)) == 8, live
+    # the four files before the rejected forms were removed: 1559 + 1242 + 69 + 44 = 2914 lines
+    assert sum(t.count("\n") for t in texts.values()) < 2914
+
+
 def test_variant_directory_binds_the_extension_to_its_own_library(lib, tmp_path):
     """An A/B variant (tools/build_variant.sh) is a directory holding its libopenstereo_amd.so and a copy of libosa_torch_ext.so; with
     OSA_LIB_PATH pointing into it, the extension loads from there and binds to the library beside it, not to the shipped one.  CPU only:
