@@ -41,6 +41,8 @@
  *                               models/msnet/MSNet2D.py:143-162, stereo/modeling/cost_volume/cost_volume.py:120-169
  *   osa_disparity_attention_f32 FoundationStereo's disparity transformer (CostVolumeDisparityAttention) in eval mode,
  *                               models/foundationstereo/core/submodule.py:540-562, fast_foundationstereo/core/submodule.py:547-603
+ *   osa_conv3d_reduced_f32      FoundationStereo's Conv3dNormActReduced (a (1,ks,ks) and a (kd,1,1) convolution, each with BatchNorm and
+ *                               ReLU) in eval mode, models/foundationstereo/core/submodule.py:87-112, fast_foundationstereo/core/submodule.py:90-115
  *   osa_geo_lookup_mr_*_f32     the multi-range lookup of IGEV++'s GRU loop (three geometry volumes of different disparity
  *                               ranges + the correlation pyramid -> four tensors), models/igevpp/geometry.py:6-87
  */
@@ -53,7 +55,7 @@
 extern "C" {
 #endif
 
-#define OSA_ABI_VERSION 17
+#define OSA_ABI_VERSION 18
 #define OSA_META_FLOATS 128   /* floats per range block (osa_f16x3_ranges) */
 
 enum { OSA_NCDHW = 0, OSA_NDHWC = 1 };
@@ -749,6 +751,25 @@ int osa_disparity_attention_pack_f32(const float* w_attn, const float* b_attn, c
                                      const float* ln, float* packed, int C, int nhead, int ff, int layers, void* stream);
 int osa_disparity_attention_f32(const float* cv, const float* pe, const float* packed, float* out, int layout, int B, int C, int L, int H, int W,
                                 int nhead, int ff, int layers, void* stream);
+
+/* ---- FoundationStereo's Conv3dNormActReduced (models/foundationstereo/core/submodule.py:87-112), ABI 18 ----
+ * Eval mode, ONE launch (csrc/conv3d_reduced.hip), the hidden tensor never in memory:
+ *   h = relu(scale1 * (conv_{1 x ks x ks}(x) + b1) + shift1)        Ci -> Ch channels, padding ks / 2, stride 1
+ *   y = relu(scale2 * (conv_{kd x 1 x 1}(h) + b2) + shift2)         Ch -> Co channels, padding kd / 2 (h is zero outside [0, D)), stride 1
+ * x and y: fp32, layout OSA_NCDHW [B,C,D,H,W] or OSA_NDHWC [B,D,H,W,C], y in x's layout and not overlapping it; packed and NDHWC tensors
+ * 16-byte aligned.  Exact fp32, no atomics, no workspace, bit-reproducible, the same bits in both layouts and for any batch size.
+ * Supported: Ci, Ch, Co multiples of 4 and <= 32, ks 1 or 3, kd odd and <= 17, any B, D, H, W >= 1.  Every error is reported before
+ * anything is launched.
+ * osa_conv3d_reduced_pack_f32: the weights in nn.Conv3d's layouts, w1 [Ch,Ci,1,ks,ks] and w2 [Co,Ch,kd,1,1], the biases b1 [Ch] and
+ * b2 [Co], and the eval-mode BatchNorm FOLDS computed by the caller (scale = weight / sqrt(running_var + eps), shift = bias -
+ * running_mean * scale); the launch folds the biases in (shift + b * scale) -> `packed`,
+ * osa_conv3d_reduced_packed_floats(Ci, Ch, Co, ks, kd) = (ks * ks + kd) * 1024 + 128 floats (every tap a 32 x 32 matrix and every vector
+ * zero padded to 32; 0 for unsupported arguments), in one small launch. */
+size_t osa_conv3d_reduced_packed_floats(int Ci, int Ch, int Co, int ks, int kd);
+int osa_conv3d_reduced_pack_f32(const float* w1, const float* b1, const float* scale1, const float* shift1, const float* w2, const float* b2,
+                                const float* scale2, const float* shift2, float* packed, int Ci, int Ch, int Co, int ks, int kd, void* stream);
+int osa_conv3d_reduced_f32(const float* x, const float* packed, float* y, int layout, int B, int D, int H, int W, int Ci, int Ch, int Co, int ks, int kd,
+                           void* stream);
 
 /* ---- input pre-processing on device ------------------------- */
 /* RightTopPad(edge) + HWC->CHW + /255 + (x-mean)/std for the left and right image in one launch

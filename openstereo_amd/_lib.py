@@ -126,6 +126,9 @@ SIGNATURES = {
     "osa_disparity_attention_pack_f32": (c_i, [c_fp] * 8 + [c_i] * 4 + [c_st]),
     "osa_interlaced_volume_pack_f32": (c_i, [c_fp] * 13 + [c_i] * 4 + [c_st]),
     "osa_interlaced_volume_f32": (c_i, [c_fp] * 4 + [c_i] * 8 + [c_st]),
+    "osa_conv3d_reduced_packed_floats": (C.c_size_t, [c_i] * 5),
+    "osa_conv3d_reduced_pack_f32": (c_i, [c_fp] * 9 + [c_i] * 5 + [c_st]),
+    "osa_conv3d_reduced_f32": (c_i, [c_fp] * 3 + [c_i] * 10 + [c_st]),
 }
 
 

@@ -207,7 +207,7 @@ def _graft(ref_cls, eng_cls, names, train_fallback=False):
 M = "stereo.modeling.models."
 
 
-def _graft_plan():
+def _graft_plan(blocks=False):        # blocks: with the rows of FoundationStereo's Conv3dNormActReduced, whose modules have a row already (without: one row per module)
     from .models import gwcnet as GW, psmnet as PSM, igev_style as IG, lightstereo as LS, igev_update as UP, msnet as MS, foundationstereo as FS
     fwd = ("forward", "forward_cl", "forward_train", "_pack", "reset_engine")
     gru = ("_packs", "new_level", "step", "_levels")          # per-level state buffers of the update block (igev_update.py)
@@ -236,7 +236,8 @@ def _graft_plan():
         *((M + mod, {c: (getattr(UP, c), fwd + gru, False) for c in ("ConvGRU", "BasicMotionEncoder", "DispHead", "BasicMultiUpdateBlock")}) for mod in ("igev.update", "stereobase.gru_blocks")),
         *((M + mod + ".core.submodule", {"CostVolumeDisparityAttention": (FS.CostVolumeDisparityAttention, ("forward", "reset_engine"), True)})   # submodule.py:540-562: eval mode only
           for mod in ("foundationstereo", "fast_foundationstereo")),
-    ]
+    ] + [(M + mod + ".core.submodule", {"Conv3dNormActReduced": (FS.Conv3dNormActReduced, ("forward", "reset_engine"), True)})               # submodule.py:87-112: eval mode only
+         for mod in ("foundationstereo", "fast_foundationstereo") if blocks]
 
 
 def patch_reference_modules(verbose: bool = False) -> list[str]:
@@ -245,7 +246,7 @@ def patch_reference_modules(verbose: bool = False) -> list[str]:
     PSMNet's stage containers and 2-D backbones, LightStereo's `Aggregation` and the IGEV / StereoBase update block.
     Works because the mirrors use the reference's attribute names."""
     done = []
-    for mod_name, classes in _graft_plan():
+    for mod_name, classes in _graft_plan(True):
         try:
             mod = importlib.import_module(mod_name)
         except Exception as ex:

@@ -321,6 +321,57 @@ at::Tensor disparity_attention(const at::Tensor& cv, const at::Tensor& pe, const
     return out;
 }
 
+// FoundationStereo's Conv3dNormActReduced in eval mode (foundationstereo/core/submodule.py:87-112; csrc/conv3d_reduced.hip).  Inference ops like
+// mv2_block3d.  w1 [Ch,Ci,1,ks,ks] and w2 [Co,Ch,kd,1,1] with their biases; scale / shift are the eval-mode BatchNorm folds (engine.bn_scale_shift).
+struct CrDims { int Ci, Ch, Co, ks, kd; };
+static CrDims cr_pack_dims(const at::Tensor& w1, const at::Tensor& w2, at::TensorList vecs) {
+    TORCH_CHECK(w1.dim() == 5 && w2.dim() == 5, "conv3d_reduced_pack: weights must be two Conv3d weights");
+    const int64_t Ch = w1.size(0), Ci = w1.size(1), ks = w1.size(3), Co = w2.size(0), kd = w2.size(2);
+    TORCH_CHECK(w1.sizes() == at::IntArrayRef({Ch, Ci, 1, ks, ks}) && w2.sizes() == at::IntArrayRef({Co, Ch, kd, 1, 1}),
+                "conv3d_reduced_pack: weights must be [Ch,Ci,1,ks,ks] and [Co,Ch,kd,1,1], got ", w1.sizes(), " and ", w2.sizes());
+    TORCH_CHECK(osa_conv3d_reduced_packed_floats((int)Ci, (int)Ch, (int)Co, (int)ks, (int)kd) > 0, "conv3d_reduced_pack: channels ", Ci, " -> ", Ch, " -> ", Co, ", kernels (1,", ks,
+                ",", ks, ") and (", kd, ",1,1) (supported: channels multiples of 4 up to 32, ks 1 or 3, kd odd up to 17)");
+    for (int i = 0; i < 6; ++i)
+        TORCH_CHECK(vecs[i].dim() == 1 && vecs[i].size(0) == (i < 3 ? Ch : Co), "conv3d_reduced_pack: vector ", i, " of (b1, scale1, shift1, b2, scale2, shift2) has shape ",
+                    vecs[i].sizes(), ", expected [", i < 3 ? Ch : Co, "]");
+    return {(int)Ci, (int)Ch, (int)Co, (int)ks, (int)kd};
+}
+at::Tensor conv3d_reduced_pack_meta(const at::Tensor& w1, const at::Tensor& b1, const at::Tensor& s1, const at::Tensor& t1, const at::Tensor& w2, const at::Tensor& b2,
+                                    const at::Tensor& s2, const at::Tensor& t2) {
+    const CrDims d = cr_pack_dims(w1, w2, {b1, s1, t1, b2, s2, t2});
+    return at::empty({(int64_t)osa_conv3d_reduced_packed_floats(d.Ci, d.Ch, d.Co, d.ks, d.kd)}, w1.options().dtype(at::kFloat));
+}
+at::Tensor conv3d_reduced_pack(const at::Tensor& w1, const at::Tensor& b1, const at::Tensor& s1, const at::Tensor& t1, const at::Tensor& w2, const at::Tensor& b2,
+                               const at::Tensor& s2, const at::Tensor& t2) {
+    at::Tensor t[8];
+    int i = 0;
+    for (const at::Tensor* s : {&w1, &b1, &s1, &t1, &w2, &b2, &s2, &t2}) t[i++] = gpu_f32(*s, "conv3d_reduced_pack argument").detach().contiguous();
+    const CrDims d = cr_pack_dims(w1, w2, {b1, s1, t1, b2, s2, t2});
+    auto packed = conv3d_reduced_pack_meta(w1, b1, s1, t1, w2, b2, s2, t2);
+    OSA_CALL(osa_conv3d_reduced_pack_f32(fp(t[0]), fp(t[1]), fp(t[2]), fp(t[3]), fp(t[4]), fp(t[5]), fp(t[6]), fp(t[7]), packed.data_ptr<float>(), d.Ci, d.Ch, d.Co, d.ks, d.kd,
+                                         cur_stream()));
+    return packed;
+}
+// -> [B,Co,D,H,W] in x's memory format: dense channels_last_3d stays so, everything else is (made) contiguous
+at::Tensor conv3d_reduced_meta(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t ks, int64_t kd) {
+    TORCH_CHECK(x.dim() == 5, "conv3d_reduced: x must be [B,Ci,D,H,W], got ", x.sizes());
+    const size_t n = osa_conv3d_reduced_packed_floats((int)x.size(1), (int)Ch, (int)Co, (int)ks, (int)kd);
+    TORCH_CHECK(n > 0, "conv3d_reduced: channels ", x.size(1), " -> ", Ch, " -> ", Co, ", kernels (1,", ks, ",", ks, ") and (", kd,
+                ",1,1) (supported: channels multiples of 4 up to 32, ks 1 or 3, kd odd up to 17)");
+    TORCH_CHECK(packed.dim() == 1 && packed.size(0) == (int64_t)n, "conv3d_reduced: packed parameters of ", packed.numel(), " floats do not belong to this configuration (", n, ")");
+    TORCH_CHECK(x.numel() > 0, "conv3d_reduced: x is empty, ", x.sizes());
+    return mr_empty(x, x.size(0), Co, x.size(2), x.size(3), x.size(4), da_channels_last(x));
+}
+at::Tensor conv3d_reduced(const at::Tensor& x, const at::Tensor& packed, int64_t Ch, int64_t Co, int64_t ks, int64_t kd) {
+    gpu_f32(x, "x"); gpu_f32(packed, "packed");
+    auto y = conv3d_reduced_meta(x, packed, Ch, Co, ks, kd);
+    const bool cl = da_channels_last(x);
+    const at::Tensor xc = cl ? x : x.contiguous();
+    OSA_CALL(osa_conv3d_reduced_f32(fp(xc), fp(packed), y.data_ptr<float>(), cl ? OSA_NDHWC : OSA_NCDHW, (int)x.size(0), (int)x.size(2), (int)x.size(3), (int)x.size(4),
+                                    (int)x.size(1), (int)Ch, (int)Co, (int)ks, (int)kd, cur_stream()));
+    return y;
+}
+
 // ---- regression heads ----------------------------------------------------------------------------------------------------------
 at::Tensor softargmin(const at::Tensor& prob) {
     gpu_f32(prob, "prob");
@@ -1420,6 +1471,8 @@ TORCH_LIBRARY(osa_native, m) {
     m.def("interlaced_volume(Tensor left, Tensor right, Tensor packed, int maxdisp, int k2, int k3, int features) -> Tensor");
     m.def("disparity_attention_pack(Tensor[] params, int nhead) -> Tensor");
     m.def("disparity_attention(Tensor cv, Tensor pe, Tensor packed, int C, int nhead, int ff, int layers) -> Tensor");
+    m.def("conv3d_reduced_pack(Tensor w1, Tensor b1, Tensor scale1, Tensor shift1, Tensor w2, Tensor b2, Tensor scale2, Tensor shift2) -> Tensor");
+    m.def("conv3d_reduced(Tensor x, Tensor packed, int Ch, int Co, int ks, int kd) -> Tensor");
     m.def("mr_volume_bwd(Tensor? dv0, Tensor? dv1, Tensor? dv2, Tensor left, Tensor right, Tensor patch0, Tensor patch1, int maxdisp, int s_range, int m_range, bool channels_last) -> (Tensor, Tensor, Tensor, Tensor)");
     m.def("concat_volume(Tensor left, Tensor right, int maxdisp, bool mask_left=True) -> Tensor");
     m.def("corr_volume(Tensor left, Tensor right, int maxdisp) -> Tensor");
@@ -1499,6 +1552,8 @@ TORCH_LIBRARY_IMPL(osa_native, CUDA, m) {        // (the HIP backend registers u
     m.impl("interlaced_volume", &interlaced_volume);
     m.impl("disparity_attention_pack", &disparity_attention_pack);
     m.impl("disparity_attention", &disparity_attention);
+    m.impl("conv3d_reduced_pack", &conv3d_reduced_pack);
+    m.impl("conv3d_reduced", &conv3d_reduced);
     m.impl("concat_volume", &concat_volume);
     m.impl("corr_volume", &corr_volume);
     m.impl("softargmin", &softargmin);
@@ -1570,6 +1625,8 @@ TORCH_LIBRARY_IMPL(osa_native, Meta, m) {        // shape / dtype inference with
     m.impl("interlaced_volume", &interlaced_volume_meta);
     m.impl("disparity_attention_pack", &disparity_attention_pack_meta);
     m.impl("disparity_attention", &disparity_attention_meta);
+    m.impl("conv3d_reduced_pack", &conv3d_reduced_pack_meta);
+    m.impl("conv3d_reduced", &conv3d_reduced_meta);
     m.impl("concat_volume", &concat_volume_meta);
     m.impl("corr_volume", &corr_volume_meta);
     m.impl("softargmin", &softargmin_meta);

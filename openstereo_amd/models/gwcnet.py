@@ -233,6 +233,10 @@ def _cb3(cin, cout, k, stride, pad):
     return nn.Sequential(nn.Conv3d(cin, cout, k, stride, pad, bias=False), nn.BatchNorm3d(cout))
 
 
+def _d3(cin, cout):
+    return nn.Sequential(nn.ConvTranspose3d(cin, cout, 3, stride=2, padding=1, output_padding=1, bias=False), nn.BatchNorm3d(cout))
+
+
 class Hourglass(nn.Module):
     """models/gwcnet/hourglass.py:19-56 (same parameter names); forward on the engine."""
 
@@ -243,12 +247,7 @@ class Hourglass(nn.Module):
         self.conv2 = nn.Sequential(_cb3(2 * c, 2 * c, 3, 1, 1), nn.ReLU(inplace=True))
         self.conv3 = nn.Sequential(_cb3(2 * c, 4 * c, 3, 2, 1), nn.ReLU(inplace=True))
         self.conv4 = nn.Sequential(_cb3(4 * c, 4 * c, 3, 1, 1), nn.ReLU(inplace=True))
-        self.conv5 = nn.Sequential(
-            nn.ConvTranspose3d(4 * c, 2 * c, 3, padding=1, output_padding=1, stride=2, bias=False),
-            nn.BatchNorm3d(2 * c))
-        self.conv6 = nn.Sequential(
-            nn.ConvTranspose3d(2 * c, c, 3, padding=1, output_padding=1, stride=2, bias=False),
-            nn.BatchNorm3d(c))
+        self.conv5, self.conv6 = _d3(4 * c, 2 * c), _d3(2 * c, c)
         self.redir1 = _cb3(c, c, 1, 1, 0)
         self.redir2 = _cb3(2 * c, 2 * c, 1, 1, 0)
         self._packed = None
@@ -300,8 +299,7 @@ STAGE_STASH = None          # a list: GwcDispProcessor.aggregate_cl / GwcNet.for
 class GwcDispProcessor(nn.Module):
     """gwcnet_disp_processor.py:29-146, inference branch, on the engine."""
 
-    def __init__(self, maxdisp=192, downsample=4, num_groups=40, use_concat_volume=True, concat_channels=12,
-                 *args, **kwargs):
+    def __init__(self, maxdisp=192, downsample=4, num_groups=40, use_concat_volume=True, concat_channels=12, *args, **kwargs):
         super().__init__()
         self.maxdisp, self.downsample, self.num_groups = maxdisp, downsample, num_groups
         self.use_concat_volume = use_concat_volume
@@ -312,8 +310,7 @@ class GwcDispProcessor(nn.Module):
         self.dres1 = nn.Sequential(_cb3(32, 32, 3, 1, 1), relu(), _cb3(32, 32, 3, 1, 1))
         self.dres2, self.dres3, self.dres4 = Hourglass(32), Hourglass(32), Hourglass(32)
         for i in range(4):
-            setattr(self, f"classif{i}", nn.Sequential(
-                _cb3(32, 32, 3, 1, 1), relu(), nn.Conv3d(32, 1, kernel_size=3, padding=1, stride=1, bias=False)))
+            setattr(self, f"classif{i}", nn.Sequential(_cb3(32, 32, 3, 1, 1), relu(), nn.Conv3d(32, 1, kernel_size=3, padding=1, stride=1, bias=False)))
         self._packed = None
 
     def reset_engine(self):
@@ -402,8 +399,7 @@ class GwcNet(nn.Module):
     def __init__(self, cfgs=GWCNET_G_SCENEFLOW):
         super().__init__()
         self.maxdisp = cfgs.MAX_DISP
-        kw = dict(maxdisp=self.maxdisp, downsample=cfgs.DOWNSAMPLE, num_groups=cfgs.NUM_GROUPS,
-                  use_concat_volume=cfgs.USE_CONCAT_VOLUME)
+        kw = dict(maxdisp=self.maxdisp, downsample=cfgs.DOWNSAMPLE, num_groups=cfgs.NUM_GROUPS, use_concat_volume=cfgs.USE_CONCAT_VOLUME)
         self.Backbone = GwcBackbone(use_concat_volume=cfgs.USE_CONCAT_VOLUME, concat_channels=cfgs.CONCAT_CHANNELS)
         self.CostProcessor = GwcVolumeCostProcessor(**kw)
         self.DispProcessor = GwcDispProcessor(concat_channels=cfgs.CONCAT_CHANNELS, **kw)

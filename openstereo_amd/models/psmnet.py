@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from .. import autograd as AG
 from .. import amp, ops, timing
 from ..engine import cached_pack, PackedConv3d, SmallCoConv3d, ACT_NONE, ACT_RELU, fold_amax
+from .gwcnet import _Cfg, _d3, GwcDispProcessor
 
 
 # ----------------------------------------------------------------------------- 2-D backbone (submodule.py factories)
@@ -47,19 +48,15 @@ class PSMBackbone(nn.Module):
 
     def __init__(self, in_planes=3):
         super().__init__()
-        self.firstconv = nn.Sequential(
-            _conv_bn(in_planes, 32, 3, 2, 1, 1, False, True), _conv_bn(32, 32, 3, 1, 1, 1, False, True),
-            _conv_bn(32, 32, 3, 1, 1, 1, False, True))
+        self.firstconv = nn.Sequential(_conv_bn(in_planes, 32, 3, 2, 1, 1, False, True), _conv_bn(32, 32, 3, 1, 1, 1, False, True), _conv_bn(32, 32, 3, 1, 1, 1, False, True))
         self._cin = 32
         self.layer1 = self._stage(32, 3, 1, 1, 1)
         self.layer2 = self._stage(64, 16, 2, 1, 1)
         self.layer3 = self._stage(128, 3, 1, 1, 1)
         self.layer4 = self._stage(128, 3, 1, 2, 2)
         for i, k in zip((1, 2, 3, 4), (64, 32, 16, 8)):
-            setattr(self, f"branch{i}", nn.Sequential(nn.AvgPool2d((k, k), stride=(k, k)),
-                                                      _conv_bn(128, 32, 1, 1, 0, 1, False, True)))
-        self.lastconv = nn.Sequential(_conv_bn(320, 128, 3, 1, 1, 1, False, True),
-                                      nn.Conv2d(128, 32, kernel_size=1, padding=0, stride=1, dilation=1, bias=False))
+            setattr(self, f"branch{i}", nn.Sequential(nn.AvgPool2d((k, k), stride=(k, k)), _conv_bn(128, 32, 1, 1, 0, 1, False, True)))
+        self.lastconv = nn.Sequential(_conv_bn(320, 128, 3, 1, 1, 1, False, True), nn.Conv2d(128, 32, kernel_size=1, padding=0, stride=1, dilation=1, bias=False))
 
     def _stage(self, cout, n, stride, pad, dil):
         ds = None
@@ -75,8 +72,7 @@ class PSMBackbone(nn.Module):
         o4 = self.layer2(o2)
         o8 = self.layer4(self.layer3(o4))
         size = (o8.size(2), o8.size(3))
-        br = [F.interpolate(getattr(self, f"branch{i}")(o8), size, mode="bilinear", align_corners=True)
-              for i in (1, 2, 3, 4)]
+        br = [F.interpolate(getattr(self, f"branch{i}")(o8), size, mode="bilinear", align_corners=True) for i in (1, 2, 3, 4)]
         return self.lastconv(torch.cat((o4, o8, br[3], br[2], br[1], br[0]), 1))
 
     # ---- engine path: every conv+BN(+ReLU)(+residual) is one fused MFMA launch on NHWC
@@ -93,8 +89,7 @@ class PSMBackbone(nn.Module):
             P = lambda cb, act: PackedConv3d(cb[0], cb[1], act)
             pk = {"first": [P(m, ACT_RELU) for m in self.firstconv], "layers": []}
             for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-                pk["layers"].append([(P(b.conv1, ACT_RELU), P(b.conv2, ACT_NONE),
-                                      None if b.downsample is None else P(b.downsample, ACT_NONE)) for b in layer])
+                pk["layers"].append([(P(b.conv1, ACT_RELU), P(b.conv2, ACT_NONE), None if b.downsample is None else P(b.downsample, ACT_NONE)) for b in layer])
             pk["branch"] = [P(getattr(self, f"branch{i}")[1], ACT_RELU) for i in (1, 2, 3, 4)]
             pk["last"] = (P(self.lastconv[0], ACT_RELU), PackedConv3d(self.lastconv[1]))
             return pk
@@ -156,11 +151,6 @@ def _c3(cin, cout, k, s, p, relu):
     if relu:
         layers.append(nn.ReLU(inplace=True))
     return nn.Sequential(*layers)
-
-
-def _d3(cin, cout):
-    return nn.Sequential(nn.ConvTranspose3d(cin, cout, 3, stride=2, padding=1, output_padding=1, bias=False),
-                         nn.BatchNorm3d(cout))
 
 
 class Hourglass(nn.Module):
@@ -225,14 +215,10 @@ class PSMAggregator(nn.Module):
         self.dres1 = nn.Sequential(_c3(32, 32, 3, 1, 1, True), _c3(32, 32, 3, 1, 1, False))
         self.dres2, self.dres3, self.dres4 = Hourglass(32), Hourglass(32), Hourglass(32)
         for i in (1, 2, 3):
-            setattr(self, f"classif{i}", nn.Sequential(_c3(32, 32, 3, 1, 1, True),
-                                                       nn.Conv3d(32, 1, kernel_size=3, stride=1, padding=1, bias=False)))
+            setattr(self, f"classif{i}", nn.Sequential(_c3(32, 32, 3, 1, 1, True), nn.Conv3d(32, 1, kernel_size=3, stride=1, padding=1, bias=False)))
         self._packed = None
 
-    def reset_engine(self):
-        self._packed = None
-        for h in (self.dres2, self.dres3, self.dres4):
-            h._packed = None
+    reset_engine = GwcDispProcessor.reset_engine          # the same three hourglasses
 
     def _pack(self):
         def build():
@@ -341,10 +327,6 @@ class PSMDispProcessor(nn.Module):
                 d, var = d
             out.append(d)
         return (out, var) if return_variance else out
-
-
-class _Cfg(dict):
-    __getattr__ = dict.__getitem__
 
 
 class PSMNet(nn.Module):
